@@ -2,6 +2,7 @@
 """bench.py — Mrays/s closest-hit on a ~1M-triangle scene, one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload soup_1m|sponza_262k|terrain_1m|soup_10m] [--obj mesh.obj] [--strong]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one pass of the hot path over one batch of synthetic rays: `rays_per_gpu` uniform-random closest-hit rays (origin
@@ -13,7 +14,11 @@ is built on the GPU by the product builder (rank 0), serialized in the reference
 over RCCL by libbvh_amd.so itself (bvhXX_broadcast); nothing else is exchanged. Weak scaling by default (every rank traces its
 own `--rays`); `--strong` splits `--rays` over the ranks (BASELINE configs[3]: 100M rays / 8).
 
-Rank 0 prints ONE JSON line (metric / value / unit / ... + "roofline" + "cpu_baseline").
+Rank 0 prints ONE JSON line (metric / value / unit / ... / ms_per_step). A plain run does only what that headline
+needs: scene, the traced tree, the rays, the library's plan search, W warm-up and K timed steps. `--full` adds everything else the
+line has carried: the OBJ round trip of the synthetic mesh, the build table of every quality ("build"), the traversal statistics and
+the roofline with its counter passes and memory probes ("roofline"), the repeated-batch pass and the CPU baseline ("cpu_baseline").
+`--dump-outputs DIR` writes the hit records of the last timed step (a fixed sample of rays) as .npy files.
 """
 from __future__ import annotations
 
@@ -40,6 +45,21 @@ WORKLOADS = {
                  "10M-tri scene"),
 }
 L2_BYTES = 8 * 4 * 1024 * 1024    # MI355X_MICROARCH.md: 4 MiB of L2 per XCD, 8 XCDs
+DUMP_RAYS = 1 << 20               # --dump-outputs: hit records of at most this many rays (28 MiB of .npy files)
+
+
+def dump_outputs(out_dir, hits):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, the (n, 4) hit records {prim, t, u, v}, for a fixed
+    sample of the rays (seeded, in ray order; every ray when n <= DUMP_RAYS), so that two builds can be compared output for output."""
+    import torch
+    n = int(hits.shape[0])
+    idx = np.arange(n) if n <= DUMP_RAYS else np.sort(np.random.default_rng(0).choice(n, DUMP_RAYS, replace=False))
+    rec = hits[torch.from_numpy(idx).to(hits.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ray_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "hit_prim.npy"), np.ascontiguousarray(rec[:, 0]).view(np.uint32).astype(np.float64))
+    for col, name in ((1, "t"), (2, "u"), (3, "v")):
+        np.save(os.path.join(out_dir, f"hit_{name}.npy"), np.ascontiguousarray(rec[:, col], dtype=np.float32))
 
 
 def parse_args():
@@ -77,6 +97,13 @@ def parse_args():
                     help="(internal) the child of a --pmc pass: build the scene, trace 1 + 3 batches with this launch plan, print nothing")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="join the N ranks, print {n_gpus, ranks} from rank 0 and exit: checks the launch path, needs no GPU (tests/test_bench_contract.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline: OBJ round trip, build table of every quality, traversal statistics, "
+                         "repeated-batch pass, roofline (counter passes, memory probes) and CPU baseline; a plain run only sets up, warms up, "
+                         "times the steps and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"after the timed steps write rank 0's hit records of the last timed step as DIR/*.npy (a fixed, seeded sample of at most "
+                         f"{DUMP_RAYS} rays): ray_index and hit_prim (INVALID = 2^32 - 1) as float64, hit_t / hit_u / hit_v as float32")
     args = ap.parse_args()
     if args.config3:
         args.workload, args.quality, args.strong, args.rays, args.serial_builder = "soup_10m", "high", True, 100_000_000, False
@@ -451,9 +478,10 @@ def through_obj(tris):
     return back, size
 
 
-def scene_and_builds(args, gen, n_tris, label):
+def scene_and_builds(args, gen, n_tris, label, full=True):
     """Rank 0 / device 0: the mesh (synthetic through an OBJ file, or --obj), every DefaultBuilder quality built and timed on the GPU,
-    the BVH of --quality and its BVH-ordered PrecomputedTri array resident in HBM."""
+    the BVH of --quality and its BVH-ordered PrecomputedTri array resident in HBM. Without `full` (a plain run): the synthetic mesh as
+    arrays and one build of --quality, untimed (builds are deterministic: the same tree)."""
     import torch
     import bvh_amd
     from bvh_amd import synth
@@ -468,16 +496,22 @@ def scene_and_builds(args, gen, n_tris, label):
         data = "Wavefront OBJ mesh + synthetic rays"
     else:
         tris = getattr(synth, gen)(n_tris)
-        if not args.no_obj_roundtrip and n_tris <= 2_000_000:
+        if full and not args.no_obj_roundtrip and n_tris <= 2_000_000:
             tris, obj_bytes = through_obj(tris)
             data = (f"synthetic mesh via OBJ (written as a {obj_bytes / 1e6:.0f} MB Wavefront OBJ, read back with the reference loader's semantics, "
                     "triangle bytes identical) + synthetic rays")
+        elif not full:
+            data = "synthetic mesh (arrays; its OBJ round trip, byte-identical, runs with --full) + synthetic rays"
         else:
             data = "synthetic mesh (arrays; OBJ round trip skipped at this size) + synthetic rays"
     d_tris = torch.from_numpy(tris).cuda()
     pool = None if args.serial_builder else bvh_amd.ThreadPool()
     builds, high_profile = {}, None
-    for qname in ("low", "medium", "high"):                               # build Mtris/s of every DefaultBuilder mode
+    if not full:                                                          # the traced tree alone: one build of --quality
+        bb, cc = bvh_amd.tri_bounds(d_tris)
+        builds[args.quality] = (None, bvh_amd.DefaultBuilder.build(bb, cc, bvh_amd.Config(quality=bvh_amd.Quality[args.quality.capitalize()]),
+                                                                   thread_pool=pool), None)
+    for qname in ("low", "medium", "high") if full else ():               # build Mtris/s of every DefaultBuilder mode
         cfg = bvh_amd.Config(quality=bvh_amd.Quality[qname.capitalize()])
         bb, cc = bvh_amd.tri_bounds(d_tris)
         bvh_q = bvh_amd.DefaultBuilder.build(bb, cc, cfg, thread_pool=pool)   # warm-up build (allocations, code load)
@@ -675,6 +709,8 @@ def one_process(args):
         t.join()
     if errors:
         raise SystemExit(f"bench.py --one-process: {errors}")
+    if args.dump_outputs:                                     # device 0's hit records of its last timed step
+        dump_outputs(args.dump_outputs, state[0]["hits"])
     per_device = [{"device": k, "rays_per_step": len(rays_h[k]), "ms_per_step": round((state[k]["t_done"] - t0) / args.steps * 1e3, 4),
                    "mrays_s": round(len(rays_h[k]) * args.steps / (state[k]["t_done"] - t0) / 1e6, 1)} for k in range(n_dev)]
     # every shard once more on device 0 alone: the sharded result must be the single-GPU result, byte for byte
@@ -827,7 +863,7 @@ def main():
     build_ms = None
     data = "synthetic"
     if rank == 0:
-        sc = scene_and_builds(args, gen, n_tris, label)
+        sc = scene_and_builds(args, gen, n_tris, label, full=args.full)
         tris, n_tris, label, data, builds, high_profile = sc["tris"], sc["n_tris"], sc["label"], sc["data"], sc["builds"], sc["high_profile"]
         build_ms, bvh, build_host_ms, prims = sc["build_ms"], sc["bvh"], sc["build_host_ms"], sc["prims"]
     else:
@@ -860,12 +896,22 @@ def main():
     n_batches = max(1, args.ray_batches)
     while n_batches > 1 and (n_batches + 2) * rays_here * 32 > 8 << 30:      # (ray memory on host and device stays below 8 GiB: --config3 on one GPU)
         n_batches -= 1
-    rays_h_all = [synth.rays_closest(rays_here, lo, hi, seed=1234 + rank + 1000 * i) for i in range(n_batches)]
+    seeds = [1234 + rank + 1000 * i for i in range(n_batches)]
+    own_settle = (n_batches + 2) * rays_here * 32 <= 8 << 30
+    if own_settle:
+        seeds += [777_000 + rank + 1000 * i for i in range(2)]
+    # the batches are independent: synthesised side by side (numpy drops the GIL), with ~200 bytes of temporaries per ray, <= 12 GiB per host
+    import concurrent.futures as cf
+    workers = max(1, min(4, len(seeds), (12 << 30) // (200 * rays_here * world)))
+    with cf.ThreadPoolExecutor(max_workers=workers) as ex:
+        made = list(ex.map(lambda s: synth.rays_closest(rays_here, lo, hi, seed=s), seeds))
+    rays_h_all = made[:n_batches]
     rays_all = [torch.from_numpy(r).cuda() for r in rays_h_all]
-    if (n_batches + 2) * rays_here * 32 > 8 << 30:
+    if not own_settle:
         settle_rays = [rays_all[0], rays_all[0]]
     else:
-        settle_rays = [torch.from_numpy(synth.rays_closest(rays_here, lo, hi, seed=777_000 + rank + 1000 * i)).cuda() for i in range(2)]
+        settle_rays = [torch.from_numpy(r).cuda() for r in made[n_batches:]]
+    del made
     rays_h, rays = rays_h_all[0], rays_all[0]
     hits = torch.empty((rays_here, 4), dtype=torch.float32, device="cuda")
 
@@ -912,9 +958,10 @@ def main():
     first_plan = (ctypes.c_int * 4)()
     lib.bvh_amd_last_launch_plan(first_plan)
 
-    # traversal statistics of this batch (stats variant of the kernel; equal to the oracle's counters, tests/)
+    # traversal statistics of this batch (stats variant of the kernel; equal to the oracle's counters, tests/); --full: they feed the roofline
+    # (a counters launch starts no plan-search measurement: the search sees the same batches either way)
     cnt = np.zeros(2, dtype=np.float64)
-    for r in rays_all:                                        # (mean over the batches the timed steps rotate through)
+    for r in rays_all if args.full else ():                   # (mean over the batches the timed steps rotate through)
         _, c1 = bvh_amd.intersect(bvh, prims, r, any_hit=False, robust=robust, counters=True, sort_rays=sort_rays)
         cnt += c1.cpu().numpy()[:2].astype(np.float64) / n_batches
     P, T = cnt[0] / rays_here, cnt[1] / rays_here
@@ -934,7 +981,7 @@ def main():
     lib.bvh_amd_last_launch_plan(plan)
     reordered = bool(plan[0])
     search = None
-    if hasattr(lib, "bvh_amd_last_plan_search"):              # what the library's plan search measured on this tree before it settled
+    if args.full and hasattr(lib, "bvh_amd_last_plan_search"):   # what the library's plan search measured on this tree before it settled
         s_ns, s_cnt, s_drop = (ctypes.c_float * 5)(), (ctypes.c_int * 5)(), ctypes.c_uint(0)
         lib.bvh_amd_last_plan_search(s_ns, s_cnt, ctypes.byref(s_drop))
         names = ["as given, per lane", "as given, cooperative", "reordered, per lane", "reordered, cooperative", "reordered, cooperative, long rays first"]
@@ -969,17 +1016,21 @@ def main():
 
     last_batch = (step_no[0] - 1) % n_batches               # whose hit records `hits` holds now (the CPU baseline checks them)
     rays_h = rays_h_all[last_batch]
-    torch.cuda.synchronize()
-    e_rep0, e_rep1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    step(rays_all[0])                                         # (untimed: the batch's first pass after other rays)
-    e_rep0.record()
-    for _ in range(args.steps):
-        step(rays_all[0])
-    e_rep1.record()
-    torch.cuda.synchronize()
-    repeated_ms = e_rep0.elapsed_time(e_rep1) / args.steps
-    step(rays_all[last_batch])                                # the checked hit records: the last timed step's batch again
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hits)
+    repeated_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        e_rep0, e_rep1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        step(rays_all[0])                                     # (untimed: the batch's first pass after other rays)
+        e_rep0.record()
+        for _ in range(args.steps):
+            step(rays_all[0])
+        e_rep1.record()
+        torch.cuda.synchronize()
+        repeated_ms = e_rep0.elapsed_time(e_rep1) / args.steps
+        step(rays_all[last_batch])                            # the checked hit records: the last timed step's batch again
+        torch.cuda.synchronize()
     mine = {"rank": rank, "rays_per_step": int(rays_here), "pass_ms": round(pass_ms, 4), "kernel_ms": round(kernel_ms, 4),
             "mrays_s": round(rays_here / pass_ms / 1e3, 1)}           # this rank's own device clock (HIP events), not the job's wall clock
     per_rank = [mine]
@@ -993,11 +1044,16 @@ def main():
     if rank == 0:
         total_rays = (args.rays if args.strong else args.rays * world) * args.steps
         value = total_rays / elapsed / 1e6
-        roofline = roofline_section(args, lib, robust=robust, rays_here=rays_here, kernel_ms=kernel_ms, pass_ms=pass_ms, reorder_ms=reorder_ms, P=P, T=T,
-                                    b_ray=b_ray, node_count=bvh.node_count, n_tris=n_tris, plan=plan, first_plan=first_plan, first_call_ms=first_call_ms,
-                                    device_index=device_index, reordered=reordered, search=search)
-        if roofline.get("first_call"):
-            roofline["first_call"]["follows_build"] = first_after_build
+        roofline = None                                       # (a plain run: "roofline", "build" and "cpu_baseline" are null, --full fills them)
+        if args.full:
+            roofline = roofline_section(args, lib, robust=robust, rays_here=rays_here, kernel_ms=kernel_ms, pass_ms=pass_ms, reorder_ms=reorder_ms, P=P, T=T,
+                                        b_ray=b_ray, node_count=bvh.node_count, n_tris=n_tris, plan=plan, first_plan=first_plan, first_call_ms=first_call_ms,
+                                        device_index=device_index, reordered=reordered, search=search)
+            if roofline.get("first_call"):
+                roofline["first_call"]["follows_build"] = first_after_build
+        repeated = ("The same {k} steps on ONE repeated batch right afterwards: {ms} ms per pass = {mr} Mrays/s on this rank (rotating: {pm} ms)".format(
+                    k=args.steps, ms=round(repeated_ms, 4), mr=round(rays_here / repeated_ms / 1e3, 1), pm=round(pass_ms, 4))
+                    if repeated_ms else "The repeated-batch pass runs with --full.")
         out = {
             "metric": f"Mrays/s closest-hit ({label})", "value": round(value, 2), "unit": "Mrays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1010,9 +1066,7 @@ def main():
                        "tris": int(n_tris), "nodes": int(bvh.node_count), "rays_per_gpu_per_step": int(rays_here),
                        "ray_batches": n_batches,
                        "ray_batches_what": f"{n_batches} distinct batches (seeds 1234 + rank + 1000 i) rotate through the warm-up and timed steps; the plan "
-                                           f"search settled on 2 other batches (seeds 777000 + ...). The same {args.steps} steps on ONE repeated batch right "
-                                           f"afterwards: {round(repeated_ms, 4)} ms per pass = {round(rays_here / repeated_ms / 1e3, 1)} Mrays/s on this rank "
-                                           f"(rotating: {round(pass_ms, 4)} ms)",
+                                           f"search settled on 2 other batches (seeds 777000 + ...). " + repeated,
                        "rays_per_step_all_gpus": int(args.rays if args.strong else args.rays * world),
                        "parallelism": (f"rays sharded x{world} ({'strong' if args.strong else 'weak'} scaling), scene broadcast once: "
                                        + bcast.get("transport", "?")) if world > 1 else "single GPU",
@@ -1020,7 +1074,7 @@ def main():
                        "launched_by": "bench.py itself (python -m torch.distributed.run, one process per GPU)"
                                       if os.environ.get("BVH_AMD_BENCH_SELF_LAUNCHED") == "1" else "torchrun environment" if world > 1 else "single process"},
             "roofline": roofline,
-            "build": build_section(n_tris, builds, high_profile, build_ms, build_host_ms, sc.get("prepare_ms")),
+            "build": build_section(n_tris, builds, high_profile, build_ms, build_host_ms, sc.get("prepare_ms")) if args.full else None,
         }
         if world > 1:
             bms = bcast.get("broadcast_ms", 0.0)
@@ -1028,7 +1082,7 @@ def main():
                                 "value_including_one_broadcast_per_run": round(total_rays / (elapsed + bms * 1e-3) / 1e6, 2),
                                 "what": "Bvh::serialize stream + BVH-ordered PrecomputedTri, device buffers, one root-to-all broadcast each (outside the timed "
                                         "steps; `value_including_one_broadcast_per_run` charges it once to the K timed steps)"}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, after the timed region, on a bounded sample (the other ranks wait at the final barrier)
             ns = min(args.cpu_sample, rays_here)
             out["cpu_baseline"] = cpu_baseline(tris, bvh, rays_h[:ns], int(robust), bvh_amd.hits_to_numpy(hits[:ns]),

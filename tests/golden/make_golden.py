@@ -2,7 +2,7 @@
 
 Run in the authoring container only (needs /root/reference and oracle/_ref/libbvh_ref.so):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [--knobs | --digests]
 
 Every array below is an output of the reference library itself (through oracle/ref_harness.cpp,
 which only #includes the reference headers), so these files pin the oracle restatement
@@ -117,6 +117,11 @@ def main():
     assert ref is not None, "needs /root/reference"
     if "--knobs" in sys.argv:                                 # only the template-knob fixture (the others are unchanged)
         template_knob_fixture(ref)
+        return
+    if "--digests" in sys.argv:                               # only ref_digests.json: tests/test_oracle_vs_ref.py compares live and records
+        import subprocess
+        subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_ref.py")],
+                       env=dict(os.environ, BVH_AMD_RECORD_REF_DIGESTS="1"), cwd=ROOT, check=True)
         return
 
     cornell = load_obj("/root/reference/test/scenes/cornell_box.obj")

@@ -48,11 +48,12 @@ class _FakeBvh:
         return self.cb.prim_ids()
 
 
-def test_bench_json_contract(monkeypatch, orc):
+def _fake_device(monkeypatch, orc):
+    """torch.cuda and the bvh_amd entry points bench.py calls, replaced by the oracle on the host; returns the shared state, whose
+    "traced" list records every closest-hit pass that writes into the caller's hit buffer (what bench.py's step() does)."""
     import torch
     import bench
     import bvh_amd
-    from bvh_amd import synth
 
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
     monkeypatch.setattr(torch.cuda, "set_device", lambda *_: None)
@@ -65,7 +66,7 @@ def test_bench_json_contract(monkeypatch, orc):
     real_tensor = torch.tensor
     monkeypatch.setattr(torch, "tensor", lambda *a, **k: real_tensor(*a, **{x: y for x, y in k.items() if x != "device"}))
 
-    state = {}
+    state = {"traced": []}
 
     def tri_bounds(t):
         state["tris"] = np.ascontiguousarray(t.numpy() if hasattr(t, "numpy") else t)
@@ -85,6 +86,8 @@ def test_bench_json_contract(monkeypatch, orc):
         if out is not None:
             out.copy_(h)
             h = out
+            if not any_hit:
+                state["traced"].append(h.clone())
         return (h, torch.from_numpy(cnt.astype(np.int64))) if counters else h
 
     monkeypatch.setattr(bvh_amd, "tri_bounds", tri_bounds)
@@ -111,16 +114,25 @@ def test_bench_json_contract(monkeypatch, orc):
     monkeypatch.setattr(bvh_amd, "last_optimize_profile", lambda: {"iterations": 3, "replayed": 2, "replacements": 1000, "heap_ms": 0.5})
     monkeypatch.setattr(bvh_amd._lib, "load", lambda: fake_lib)
     monkeypatch.setitem(bench.WORKLOADS, "soup_1m", ("soup", 3000, "tiny stand-in scene of the contract test", "3000-tri stand-in"))
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--rays", "4096", "--cpu-sample", "2048", "--no-probe", "--no-pmc"])
     for var in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(var, raising=False)
+    return state
 
+
+def _run_bench(monkeypatch, argv):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
     buf = io.StringIO()
     with redirect_stdout(buf):
         bench.main()
     lines = [l for l in buf.getvalue().splitlines() if l.startswith("{")]
     assert len(lines) == 1, "rank 0 prints exactly one JSON line"
-    out = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_json_contract(monkeypatch, orc):
+    _fake_device(monkeypatch, orc)
+    out = _run_bench(monkeypatch, ["--steps", "3", "--warmup", "1", "--rays", "4096", "--cpu-sample", "2048", "--no-probe", "--no-pmc", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
                 "data", "config", "roofline", "cpu_baseline", "build"):
         assert key in out, key
@@ -154,6 +166,35 @@ def test_bench_json_contract(monkeypatch, orc):
         assert abs(r["bytes_per_tri"] - (76.0 + 76.0 * r["mean_split_ancestors"] + 28.0 * out["config"]["nodes"] / 3000)) < 60.0
     assert set(b["all_qualities_ms"]) == {"low", "medium", "high"} and b["ms_with_host_mirror"] >= b["ms"] > 0
     assert b["high"]["iterations"] == 3 and b["high"]["replayed"] == 2 and abs(b["high"]["us_per_replacement"] - 0.5) < 1e-6
+
+
+def test_plain_bench_line_and_dump_outputs(monkeypatch, orc, tmp_path):
+    """A plain run (no --full) traces the settling batches, W warm-up and exactly K timed steps and nothing else; its line carries the
+    headline fields, and --dump-outputs writes the hit records of the last timed step, in float32 / float64, for a fixed ray sample."""
+    import bench
+    state = _fake_device(monkeypatch, orc)
+    monkeypatch.setattr(bench, "DUMP_RAYS", 1000)                               # a sample smaller than the batch
+    out = _run_bench(monkeypatch, ["--steps", "5", "--warmup", "2", "--rays", "4096", "--dump-outputs", str(tmp_path / "o")])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert key in out, key
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["unit"] == "Mrays/s" and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert out["metric"] == "Mrays/s closest-hit (3000-tri stand-in)" and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["roofline"] is None and out["build"] is None and out["cpu_baseline"] is None
+    assert "via OBJ" not in out["data"]
+    assert len(state["traced"]) == 1 + 12 + 2 + 5                              # first call, 12 settling passes, W, K: nothing after the K steps
+    files = {p.name: np.load(p) for p in (tmp_path / "o").iterdir()}
+    assert set(files) == {"ray_index.npy", "hit_prim.npy", "hit_t.npy", "hit_u.npy", "hit_v.npy"}
+    assert all(a.dtype in (np.float32, np.float64) and a.shape == (1000,) for a in files.values())
+    idx = files["ray_index.npy"].astype(np.int64)
+    assert (np.diff(idx) > 0).all() and idx[-1] < 4096
+    last = state["traced"][-1].numpy()[idx]
+    assert (files["hit_prim.npy"] == last[:, 0].view(np.uint32)).all() and (files["hit_prim.npy"] != oracle.INVALID).any()
+    for col, name in ((1, "t"), (2, "u"), (3, "v")):
+        assert files[f"hit_{name}.npy"].tobytes() == np.ascontiguousarray(last[:, col]).tobytes()
+    again = tmp_path / "again"                                                  # same arguments: same sample, same inputs, same outputs
+    _run_bench(monkeypatch, ["--steps", "5", "--warmup", "2", "--rays", "4096", "--dump-outputs", str(again)])
+    for name, a in files.items():
+        assert np.load(again / name).tobytes() == a.tobytes(), name
 
 
 def test_bench_starts_its_own_ranks():

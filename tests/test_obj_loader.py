@@ -43,9 +43,8 @@ def test_obj_round_trip_and_reference_cornell_box(tmp_path):
     p = tmp_path / "r.obj"
     obj.save_obj(str(p), tris)
     assert obj.load_obj(str(p)).tobytes() == tris.tobytes()                       # %.9g round-trips float32 through strtof
-    ref = "/root/reference/test/cornell_box.obj"
-    if os.path.exists(ref):                                                       # the authoring container: the golden fixture's triangles
-        assert obj.load_obj(ref).tobytes() == load_golden("cornell")["prims"].tobytes()
+    cornell = os.path.join(ROOT, "tests", "golden", "cornell_box.obj")            # the reference's scene file: the golden fixture's triangles
+    assert obj.load_obj(cornell).tobytes() == load_golden("cornell")["prims"].tobytes()
     assert obj.load_obj(str(tmp_path / "missing.obj") if False else str(p)).shape[1] == 9
     empty = tmp_path / "e.obj"
     empty.write_text("v 0 0 0\n")

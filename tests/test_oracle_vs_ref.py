@@ -1,11 +1,49 @@
-"""Restatement vs the compiled, unmodified reference on seeded inputs (authoring container only:
-needs oracle/_ref/libbvh_ref.so, which can only be built where /root/reference exists)."""
+"""Restatement vs the compiled, unmodified reference on seeded inputs. Where oracle/_ref/libbvh_ref.so loads (it is built where the
+reference sources are), the reference computes every compared output live and the bytes must be equal. Everywhere, the restatement's
+bytes must have the SHA-256 digests the reference's outputs had (tests/golden/ref_digests.json, written by
+`python tests/golden/make_golden.py --digests` where the reference library loads)."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
 import oracle
 from bvh_amd import synth
-from conftest import MODES
+from conftest import GOLDEN, MODES
+
+DIGESTS = os.path.join(GOLDEN, "ref_digests.json")
+RECORD = os.environ.get("BVH_AMD_RECORD_REF_DIGESTS") == "1"        # (make_golden.py --digests sets it; needs the reference library)
+
+
+class Pin:
+    """pin(tag, mine, theirs): `mine` is the restatement's output (bytes), `theirs` computes the reference's (None without oracle/_ref)."""
+
+    def __init__(self, ref):
+        self.ref = ref
+        self.digests = json.load(open(DIGESTS)) if os.path.exists(DIGESTS) else {}
+        self.recorded = {}
+
+    def __call__(self, tag, mine, theirs=None):
+        if self.ref is not None and theirs is not None:
+            assert theirs() == mine, tag
+        digest = hashlib.sha256(mine).hexdigest()
+        if RECORD:
+            assert self.ref is not None and tag not in self.recorded, tag
+            self.recorded[tag] = digest
+        else:
+            assert self.digests.get(tag) == digest, tag
+
+
+@pytest.fixture(scope="module")
+def pin():
+    p = Pin(oracle.load_ref())
+    yield p
+    if RECORD:
+        with open(DIGESTS, "w") as f:
+            json.dump(dict(sorted(p.recorded.items())), f, indent=0)
+            f.write("\n")
 
 
 def _scene(name):
@@ -18,160 +56,177 @@ def _scene(name):
     raise KeyError(name)
 
 
+def _b(*arrays):
+    return b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
+
+
 @pytest.mark.parametrize("scene", ["soup", "terrain", "sponza"])
-def test_builders_and_traversal_match_reference(orc, ref, scene):
+def test_builders_and_traversal_match_reference(orc, pin, scene):
+    ref = pin.ref
     tris = _scene(scene)
-    bb, cc = ref.prep_tris(tris)
-    bb2, cc2 = orc.prep_tris(tris)
-    assert bb.tobytes() == bb2.tobytes() and cc.tobytes() == cc2.tobytes()
+    bb, cc = orc.prep_tris(tris)
+    pin(f"{scene}/prep", _b(bb, cc), ref and (lambda: _b(*ref.prep_tris(tris))))
     lo, hi = synth.scene_bounds(tris)
     rays = synth.rays_closest(5000, lo, hi)
     srays = synth.rays_shadow(5000, lo, hi)
     for mode, builder, quality in MODES:
-        a = ref.build(bb, cc, builder=builder, quality=quality, threads=3)
         b = orc.build(bb, cc, builder=builder, quality=quality)
-        assert a.serialize() == b.serialize(), mode
-    pa, pb = ref.precompute_tris(tris, a.prim_ids()), orc.precompute_tris(tris, b.prim_ids())
-    assert pa.tobytes() == pb.tobytes()
+        a = ref and ref.build(bb, cc, builder=builder, quality=quality, threads=3)
+        pin(f"{scene}/{mode}", b.serialize(), a and a.serialize)
+    pb = orc.precompute_tris(tris, b.prim_ids())
+    pin(f"{scene}/precompute", pb.tobytes(), a and (lambda: ref.precompute_tris(tris, a.prim_ids()).tobytes()))
     for any_hit in (0, 1):
         for robust in (0, 1):
             rr = srays if any_hit else rays
-            ha, ca = a.intersect_tri(pa, rr, any_hit, robust, counters=True)
             hb, cb = b.intersect_tri(pb, rr, any_hit, robust, counters=True)
-            assert ha.tobytes() == hb.tobytes() and (ca == cb).all()
+            pin(f"{scene}/trace/{any_hit}{robust}", _b(hb, cb), a and (lambda: _b(*a.intersect_tri(pb, rr, any_hit, robust, counters=True))))
 
 
-def test_double_spheres_match_reference(orc, ref):
+def test_double_spheres_match_reference(orc, pin):
+    ref = pin.ref
     sph = synth.spheres(8000, rmin=0.005, rmax=0.02)
-    bb, cc = ref.sphere_bboxes(sph)
-    bb2, cc2 = orc.sphere_bboxes(sph)
-    assert bb.tobytes() == bb2.tobytes() and cc.tobytes() == cc2.tobytes()
-    a = ref.build(bb, cc, builder=1, quality=2, threads=3)
+    bb, cc = orc.sphere_bboxes(sph)
+    pin("spheres/bboxes", _b(bb, cc), ref and (lambda: _b(*ref.sphere_bboxes(sph))))
     b = orc.build(bb, cc, builder=1, quality=2)
-    assert a.serialize() == b.serialize()
-    perm = a.prim_ids().astype(np.int64)
+    a = ref and ref.build(bb, cc, builder=1, quality=2, threads=3)
+    pin("spheres/build", b.serialize(), a and a.serialize)
+    perm = b.prim_ids().astype(np.int64)
     lo, hi = synth.scene_bounds(sph)
     rays = synth.rays_closest(5000, lo, hi, dtype=np.float64)
     for any_hit in (0, 1):
         for robust in (0, 1):
-            ha, ca = a.intersect_sphere(sph[perm], rays, any_hit, robust, counters=True)
             hb, cb = b.intersect_sphere(sph[perm], rays, any_hit, robust, counters=True)
-            assert ha.tobytes() == hb.tobytes() and (ca == cb).all()
+            pin(f"spheres/trace/{any_hit}{robust}", _b(hb, cb), a and (lambda: _b(*a.intersect_sphere(sph[perm], rays, any_hit, robust, counters=True))))
 
 
-def test_optimize_and_refit_match_reference(orc, ref):
+def test_optimize_and_refit_match_reference(orc, pin):
+    ref = pin.ref
     tris = synth.soup(6000, seed=9, jitter=0.03)
-    bb, cc = ref.prep_tris(tris)
-    a = ref.build(bb, cc, builder=oracle.BUILDER_SWEEP)
+    bb, cc = orc.prep_tris(tris)
     b = orc.build(bb, cc, builder=oracle.BUILDER_SWEEP)
-    a.optimize(-1)
-    b.optimize(-1)
-    assert a.serialize() == b.serialize()
-    a.optimize(3)
-    b.optimize(3)
-    assert a.serialize() == b.serialize()
-    a.refit()
+    a = ref and ref.build(bb, cc, builder=oracle.BUILDER_SWEEP)
+    for tag, threads in (("optimize_serial", -1), ("optimize_3", 3)):
+        b.optimize(threads)
+        if a:
+            a.optimize(threads)
+        pin(f"soup6k/{tag}", b.serialize(), a and a.serialize)
     b.refit()
-    assert a.serialize() == b.serialize()
+    if a:
+        a.refit()
+    pin("soup6k/refit", b.serialize(), a and a.serialize)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-def test_2d_restatement_matches_reference(orc, ref, dtype):
+def test_2d_restatement_matches_reference(orc, pin, dtype):
     """Node<T, 2>: every serial builder, optimize, extract_bvh, refit and the four traversal modes with circles."""
+    ref = pin.ref
+    d = np.dtype(dtype).name
     circ = synth.circles(12000, dtype=dtype, rmin=0.001, rmax=0.01)
-    bb, cc = ref.sphere_bboxes(circ)
-    bb2, cc2 = orc.sphere_bboxes(circ)
-    assert bb.tobytes() == bb2.tobytes() and cc.tobytes() == cc2.tobytes()
+    bb, cc = orc.sphere_bboxes(circ)
+    pin(f"2d_{d}/bboxes", _b(bb, cc), ref and (lambda: _b(*ref.sphere_bboxes(circ))))
     for builder in (oracle.BUILDER_DEFAULT_SERIAL, oracle.BUILDER_BINNED, oracle.BUILDER_SWEEP):
         for quality in (0, 1, 2):
-            a = ref.build(bb, cc, builder=builder, quality=quality)
             b = orc.build(bb, cc, builder=builder, quality=quality)
-            assert a.serialize() == b.serialize() and a.nodes().dtype.itemsize == (20 if dtype == np.float32 else 40)
-    a, b = ref.build(bb, cc, builder=oracle.BUILDER_BINNED), orc.build(bb, cc, builder=oracle.BUILDER_BINNED)
-    for _ in range(2):
-        a.optimize(-1)
+            assert b.nodes().dtype.itemsize == (20 if dtype == np.float32 else 40)
+            pin(f"2d_{d}/build/{builder}{quality}", b.serialize(), ref and (lambda: ref.build(bb, cc, builder=builder, quality=quality).serialize()))
+    b = orc.build(bb, cc, builder=oracle.BUILDER_BINNED)
+    a = ref and ref.build(bb, cc, builder=oracle.BUILDER_BINNED)
+    for i in range(2):
         b.optimize(-1)
-        assert a.serialize() == b.serialize()
-    assert a.extract(5).serialize() == b.extract(5).serialize()
-    a.refit()
+        if a:
+            a.optimize(-1)
+        pin(f"2d_{d}/optimize{i}", b.serialize(), a and a.serialize)
+    pin(f"2d_{d}/extract5", b.extract(5).serialize(), a and (lambda: a.extract(5).serialize()))
     b.refit()
-    assert a.serialize() == b.serialize()
-    pp = circ[a.prim_ids().astype(np.int64)]
+    if a:
+        a.refit()
+    pin(f"2d_{d}/refit", b.serialize(), a and a.serialize)
+    pp = circ[b.prim_ids().astype(np.int64)]
     for any_hit, rays in ((0, synth.rays_2d(5000, dtype=dtype)), (1, synth.rays_2d(5000, dtype=dtype, segment=True))):
         for robust in (0, 1):
-            ha, ca = a.intersect_sphere(pp, rays, any_hit, robust, counters=True)
             hb, cb = b.intersect_sphere(pp, rays, any_hit, robust, counters=True)
-            assert ha.tobytes() == hb.tobytes() and (ca == cb).all()
+            pin(f"2d_{d}/trace/{any_hit}{robust}", _b(hb, cb), a and (lambda: _b(*a.intersect_sphere(pp, rays, any_hit, robust, counters=True))))
 
 
-def test_minitree_builder_direct_matches_reference(orc, ref):
+def test_minitree_builder_direct_matches_reference(orc, pin):
+    ref = pin.ref
     tris = synth.sponza_proxy(30000)
-    bb, cc = ref.prep_tris(tris)
+    bb, cc = orc.prep_tris(tris)
     for kw in (dict(), dict(enable_pruning=False), dict(pruning_area_ratio=0.3), dict(pruning_area_ratio=1.5, max_leaf=4),
                dict(parallel_threshold=200, pruning_area_ratio=0.05)):
-        assert ref.build_minitree(bb, cc, threads=3, **kw).serialize() == orc.build_minitree(bb, cc, **kw).serialize(), kw
+        pin(f"minitree/{sorted(kw.items())}", orc.build_minitree(bb, cc, **kw).serialize(),
+            ref and (lambda: ref.build_minitree(bb, cc, threads=3, **kw).serialize()))
     for L in (1, 3, 6):
         for kw in (dict(), dict(enable_pruning=False), dict(parallel_threshold=0)):
-            assert ref.build_minitree(bb, cc, threads=2, log2_grid_dim=L, **kw).serialize() == orc.build_minitree(bb, cc, log2_grid_dim=L, **kw).serialize(), (L, kw)
+            pin(f"minitree/grid{L}/{sorted(kw.items())}", orc.build_minitree(bb, cc, log2_grid_dim=L, **kw).serialize(),
+                ref and (lambda: ref.build_minitree(bb, cc, threads=2, log2_grid_dim=L, **kw).serialize()))
     for n in (1, 2, 9, 300):
         t = synth.soup(n, jitter=0.05)
-        b2, c2 = ref.prep_tris(t)
-        assert ref.build_minitree(b2, c2, threads=2).serialize() == orc.build_minitree(b2, c2).serialize(), n
+        b2, c2 = orc.prep_tris(t)
+        pin(f"minitree/n{n}", orc.build_minitree(b2, c2).serialize(), ref and (lambda: ref.build_minitree(b2, c2, threads=2).serialize()))
 
 
-def test_split_heuristic_and_optimizer_config_match_reference(orc, ref):
+def test_split_heuristic_and_optimizer_config_match_reference(orc, pin):
     """TopDownSahBuilder::Config::sah (split_heuristic.h:17-38) through every builder, and ReinsertionOptimizer::Config
     (reinsertion_optimizer.h:18-24): the restatement against the compiled reference."""
+    ref = pin.ref
     tris = synth.sponza_proxy(20000)
-    bb, cc = ref.prep_tris(tris)
+    bb, cc = orc.prep_tris(tris)
     for log, ratio in ((1, 1.0), (3, 0.5), (0, 2.0), (2, 3.0), (0, -1.0)):
         orc.set_sah(log, ratio)
-        ref.set_sah(log, ratio)
+        if ref:
+            ref.set_sah(log, ratio)
         try:
             for builder, quality in ((2, 0), (3, 0), (0, 2), (1, 0), (1, 2)):
-                assert ref.build(bb, cc, builder=builder, quality=quality, threads=2).serialize() == \
-                    orc.build(bb, cc, builder=builder, quality=quality).serialize(), (log, ratio, builder, quality)
-            assert ref.build_minitree(bb, cc, threads=2, pruning_area_ratio=0.2, parallel_threshold=300).serialize() == \
-                orc.build_minitree(bb, cc, pruning_area_ratio=0.2, parallel_threshold=300).serialize(), (log, ratio)
+                pin(f"sah{log},{ratio}/{builder}{quality}", orc.build(bb, cc, builder=builder, quality=quality).serialize(),
+                    ref and (lambda: ref.build(bb, cc, builder=builder, quality=quality, threads=2).serialize()))
+            pin(f"sah{log},{ratio}/minitree", orc.build_minitree(bb, cc, pruning_area_ratio=0.2, parallel_threshold=300).serialize(),
+                ref and (lambda: ref.build_minitree(bb, cc, threads=2, pruning_area_ratio=0.2, parallel_threshold=300).serialize()))
         finally:
             orc.set_sah()
-            ref.set_sah()
+            if ref:
+                ref.set_sah()
     for ratio, iters in ((0.01, 1), (0.2, 2), (1.0, 1), (3.0, 2), (0.0, 4), (0.5, 0), (0.3, 7)):
-        a, b = ref.build(bb, cc, quality=1), orc.build(bb, cc, quality=1)
-        a.optimize(threads=2, batch_size_ratio=ratio, max_iter_count=iters)
+        b = orc.build(bb, cc, quality=1)
         b.optimize(batch_size_ratio=ratio, max_iter_count=iters)
-        assert a.serialize() == b.serialize(), (ratio, iters)
+        a = ref and ref.build(bb, cc, quality=1)
+        if a:
+            a.optimize(threads=2, batch_size_ratio=ratio, max_iter_count=iters)
+        pin(f"optimizer{ratio},{iters}", b.serialize(), a and a.serialize)
 
 
 @pytest.mark.parametrize("bins", [4, 16, 32])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-def test_binned_builder_bin_counts_match_reference(orc, ref, bins, dtype):
+def test_binned_builder_bin_counts_match_reference(orc, pin, bins, dtype):
     """BinnedSahBuilder<Node, BinCount> (binned_sah_builder.h:18): the restatement's run-time bin count against the reference's
     template instantiations, 3D and 2D, default and non-default leaf limits / SplitHeuristic."""
+    ref = pin.ref
+    d = np.dtype(dtype).name
+    libs = [orc] + ([ref] if ref else [])
     try:
         for name in ("soup", "terrain", "sponza"):
             tris = _scene(name).astype(dtype)
-            bb, cc = ref.prep_tris(tris)
-            ref.set_bin_count(bins)
-            orc.set_bin_count(bins)
+            bb, cc = orc.prep_tris(tris)
+            for lib in libs:
+                lib.set_bin_count(bins)
             for min_leaf, max_leaf, sah in ((1, 8, (0, 1.0)), (2, 5, (1, 0.7))):
-                ref.set_sah(*sah)
-                orc.set_sah(*sah)
-                a = ref.build(bb, cc, builder=oracle.BUILDER_BINNED, min_leaf=min_leaf, max_leaf=max_leaf)
+                for lib in libs:
+                    lib.set_sah(*sah)
                 b = orc.build(bb, cc, builder=oracle.BUILDER_BINNED, min_leaf=min_leaf, max_leaf=max_leaf)
-                assert a.serialize() == b.serialize(), (name, min_leaf, max_leaf, sah)
-            ref.set_sah()
-            orc.set_sah()
+                pin(f"bins{bins}_{d}/{name}/{min_leaf},{max_leaf},{sah}", b.serialize(),
+                    ref and (lambda: ref.build(bb, cc, builder=oracle.BUILDER_BINNED, min_leaf=min_leaf, max_leaf=max_leaf).serialize()))
+            for lib in libs:
+                lib.set_sah()
             # a different bin count really is a different tree
-            ref.set_bin_count(8)
-            assert ref.build(bb, cc, builder=oracle.BUILDER_BINNED).serialize() != a.serialize()
+            orc.set_bin_count(8)
+            assert orc.build(bb, cc, builder=oracle.BUILDER_BINNED).serialize() != b.serialize()
         circ = synth.circles(3000, dtype=dtype, rmin=0.001, rmax=0.01)               # Node<T, 2>
-        bb2, cc2 = ref.sphere_bboxes(circ)
-        ref.set_bin_count(bins)
-        orc.set_bin_count(bins)
-        assert ref.build(bb2, cc2, builder=oracle.BUILDER_BINNED).serialize() == orc.build(bb2, cc2, builder=oracle.BUILDER_BINNED).serialize()
+        bb2, cc2 = orc.sphere_bboxes(circ)
+        for lib in libs:
+            lib.set_bin_count(bins)
+        pin(f"bins{bins}_{d}/circles", orc.build(bb2, cc2, builder=oracle.BUILDER_BINNED).serialize(),
+            ref and (lambda: ref.build(bb2, cc2, builder=oracle.BUILDER_BINNED).serialize()))
     finally:
-        ref.set_bin_count(8)
-        orc.set_bin_count(8)
-        ref.set_sah()
-        orc.set_sah()
+        for lib in libs:
+            lib.set_bin_count(8)
+            lib.set_sah()
