@@ -30,6 +30,8 @@ namespace {
 struct WalkRec { uint32_t w[16]; };
 
 __device__ inline bool lane_active(uint32_t lane, uint32_t active) { return ((lane * 37u) & 63u) < active; }
+// the byte count coop_load_pair's buffer descriptor wants for a table of n 64-byte records (its 32-bit offsets reach 2^26 records)
+__device__ inline uint32_t walk_bytes(uint32_t n) { return static_cast<uint32_t>(min(n * 64ull, static_cast<unsigned long long>(kNoRecordAt))); }
 
 __global__ void __launch_bounds__(256) k_record_walk(const WalkRec* table, uint32_t n_rec, uint32_t steps, uint32_t active, unsigned long long* sink) {
     const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
@@ -82,8 +84,8 @@ __global__ void __launch_bounds__(256) k_record_walk_dpp2(const WalkRec* table, 
     for (uint32_t it = 0; it < steps; ++it) {
         float lb0[6], rb0[6], lb1[6], rb1[6];
         uint32_t li0 = 0, ri0 = 0, li1 = 0, ri1 = 0;
-        coop_load_pair(reinterpret_cast<const PairNode<float>*>(table), mine ? i0 : 0xFFFFFFFFu, static_cast<int>(lane), lb0, rb0, li0, ri0);
-        coop_load_pair(reinterpret_cast<const PairNode<float>*>(table), mine ? i1 : 0xFFFFFFFFu, static_cast<int>(lane), lb1, rb1, li1, ri1);
+        coop_load_pair(reinterpret_cast<const PairNode<float>*>(table), walk_bytes(n_rec), mine ? i0 : 0xFFFFFFFFu, static_cast<int>(lane), lb0, rb0, li0, ri0);
+        coop_load_pair(reinterpret_cast<const PairNode<float>*>(table), walk_bytes(n_rec), mine ? i1 : 0xFFFFFFFFu, static_cast<int>(lane), lb1, rb1, li1, ri1);
         if (mine) {
             acc += ((lb0[1] + lb0[2]) + (lb0[3] + lb0[4])) + ((lb0[5] + rb0[0]) + (rb0[1] + rb0[2])) + ((rb0[3] + rb0[4]) + rb0[5]);
             acc += ((lb1[1] + lb1[2]) + (lb1[3] + lb1[4])) + ((lb1[5] + rb1[0]) + (rb1[1] + rb1[2])) + ((rb1[3] + rb1[4]) + rb1[5]);
@@ -163,7 +165,7 @@ __global__ void __launch_bounds__(256) k_record_walk_dpp(const WalkRec* table, u
     for (uint32_t it = 0; it < steps; ++it) {
         float lb[6], rb[6];
         uint32_t li = 0, ri = 0;
-        coop_load_pair(reinterpret_cast<const PairNode<float>*>(table), mine ? idx : 0xFFFFFFFFu, static_cast<int>(lane), lb, rb, li, ri);
+        coop_load_pair(reinterpret_cast<const PairNode<float>*>(table), walk_bytes(n_rec), mine ? idx : 0xFFFFFFFFu, static_cast<int>(lane), lb, rb, li, ri);
         if (mine) {
             acc += ((lb[1] + lb[2]) + (lb[3] + lb[4])) + ((lb[5] + rb[0]) + (rb[1] + rb[2])) + ((rb[3] + rb[4]) + rb[5]);   // every word is used
             const uint32_t next = __float_as_uint(lb[0]);     // w[0]
@@ -217,7 +219,7 @@ __global__ void __launch_bounds__(256) k_record_walk_mixed(const WalkRec* small_
         const uint32_t idx = (small_step ? is : ib) + carry;   // carry == 0, but only the previous fetch says so
         float lb[6], rb[6];
         uint32_t li = 0, ri = 0;
-        if (Coop) coop_load_pair(reinterpret_cast<const PairNode<float>*>(t), idx, static_cast<int>(lane), lb, rb, li, ri);
+        if (Coop) coop_load_pair(reinterpret_cast<const PairNode<float>*>(t), walk_bytes(small_step ? n_small : n_big), idx, static_cast<int>(lane), lb, rb, li, ri);
         else load_pair(reinterpret_cast<const PairNode<float>*>(t) + idx, lb, rb, li, ri);
         acc += ((lb[1] + lb[2]) + (lb[3] + lb[4])) + ((lb[5] + rb[0]) + (rb[1] + rb[2])) + ((rb[3] + rb[4]) + rb[5]);
         const uint32_t next = __float_as_uint(lb[0]);

@@ -156,7 +156,7 @@
             uint32_t li = 0, ri = 0;
             // Coop: the four lanes of a quad fetch each other's records, one line request per record instead of four lane
             // requests (trace_device.h: coop_load_pair); idle and parked lanes only help loading
-            if constexpr (BVH_TRACE_COOP) coop_load_pair(a.pairs, inner ? (top >> (kCountBits + 1)) : 0xFFFFFFFFu, lane, lb, rb, li, ri);
+            if constexpr (BVH_TRACE_COOP) coop_load_pair(a.pairs, a.pair_bytes, inner ? (top >> (kCountBits + 1)) : 0xFFFFFFFFu, lane, lb, rb, li, ri);
             if (inner) {
                 if constexpr (!BVH_TRACE_COOP) load_pair(a.pairs + (top >> (kCountBits + 1)), lb, rb, li, ri);
                 if (Stats) ++n_pairs;

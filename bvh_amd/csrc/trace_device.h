@@ -108,6 +108,7 @@ struct TraceArgs {
     uint32_t one_shot;                         // 1: grid = ceil(n / 256) blocks, wave w traces rays [64 w, 64 w + 64) and leaves (small batches)
     unsigned long long* wave_times;            // developer library only (bvh_amd_experiment("wave_times", 1)): per wave {begin, last refill, end, xcc | rays, ticks inside refills, refills} in
                                                // s_memrealtime ticks (100 MHz) + {XCC id, rays traced}; nullptr otherwise — the release kernels never read it
+    uint32_t pair_bytes = 0;                   // bytes of `pairs`: the size of the cooperative fetch's buffer descriptor (device only)
 };
 
 __device__ inline void load_pair(const PairNode<float>* p, float (&lb)[6], float (&rb)[6], uint32_t& li, uint32_t& ri) {
@@ -133,7 +134,7 @@ __device__ inline void load_pair(const PairNode<double>* p, double (&lb)[6], dou
 // cost four requests, and measured (csrc/probe.hip, tools/tcp_probe.py) a wave-instruction takes ~8.5 clk + 0.56 clk per distinct
 // line request: ~2.8 clk per record at 64 active lanes, 3.5 at 28 — while a QUAD whose four lanes read the four 16-byte chunks of
 // ONE record is a single line request (0.95 lines / clk / CU). So the four lanes of a quad fetch each other's records: in
-// instruction k every lane loads chunk (lane & 3) of the record wanted by the quad's lane k (skipped when that lane wants none),
+// instruction k every lane loads chunk (lane & 3) of the record wanted by the quad's lane k (zeros, and no request, when that lane wants none),
 // and a 4 x 4 transpose inside the quad — two butterfly stages of DPP quad_perm moves, no LDS — hands every lane the four chunks
 // of its own record. Requests per visited record: 1 instead of 4. Every lane of the wave must call this (wave-uniform control flow).
 #if defined(__HIPCC__)
@@ -194,20 +195,39 @@ template <bool ByTwo> inline void quad_exchange4(uint32_t (&a)[4], uint32_t (&b)
     }
 }
 #endif
+// The record loads of coop_load_pair<float>: raw buffer loads through a descriptor whose size is the records' exact byte count. A
+// lane that wants no record (0xFFFFFFFF) asks for byte offset kNoRecordAt + chunk, at or beyond the end of every tree the cooperative
+// kernel takes (launch_variant: fewer than 2^26 records, so at most 2^32 - 64 bytes), and the range check returns zeros for it. So the
+// four loads need no per-lane guard: no exec mask, no branch around them. (Measured on the bench kernel, profiles/r07_pmc_*.csv: the
+// out-of-range lanes add no L1 accesses or L2 read requests — TCP_TOTAL_CACHE_ACCESSES and TCP_TCC_READ_REQ per launch unchanged.)
+constexpr uint32_t kNoRecordAt = 0xFFFFFFFFu << 6;
+#if defined(__HIPCC__)
+// (0x00020000: the descriptor's last word on gfx9 — DATA_FORMAT 32, no swizzle, no index stride: the size counts bytes)
+using PairRsrc = __amdgpu_buffer_rsrc_t;
+__device__ inline PairRsrc pair_rsrc(const void* base, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, static_cast<int>(bytes), 0x00020000);
+}
+__device__ inline uint4 load_chunk(PairRsrc r, uint32_t at) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, static_cast<int>(at), 0, 0);
+    return uint4{v[0], v[1], v[2], v[3]};
+}
+#elif defined(BVH_HOST_WAVE64)
+// tests/cpp/trace_body_host.cpp: the same loads by their meaning (zeros beyond the records; the host never reads the size).
+struct PairRsrc { const char* base; };
+inline PairRsrc pair_rsrc(const void* base, uint32_t) { return PairRsrc{static_cast<const char*>(base)}; }
+inline uint4 load_chunk(PairRsrc r, uint32_t at) {
+    if (at >= kNoRecordAt) return uint4{0, 0, 0, 0};
+    return *reinterpret_cast<const uint4*>(r.base + at);
+}
+#endif
 #if defined(__HIPCC__) || defined(BVH_HOST_WAVE64)
-__device__ inline void coop_load_pair(const PairNode<float>* pairs, uint32_t want, int lane, float (&lb)[6], float (&rb)[6], uint32_t& li, uint32_t& ri) {
-    constexpr uint32_t kNone = 0xFFFFFFFFu;
-    const uint32_t j = static_cast<uint32_t>(lane) & 3u;
-    const uint32_t o0 = quad_perm<0x00>(want), o1 = quad_perm<0x55>(want), o2 = quad_perm<0xAA>(want), o3 = quad_perm<0xFF>(want);
-    // (uniform base + 32-bit byte offset: the loads take the SGPR-base form and need no 64-bit address arithmetic per lane;
-    //  launch_variant only selects this kernel for trees of fewer than 2^26 pair records)
-    const char* base = reinterpret_cast<const char*>(pairs);
-    const uint32_t chunk = j * 16u;
-    uint4 c0 = {0, 0, 0, 0}, c1 = {0, 0, 0, 0}, c2 = {0, 0, 0, 0}, c3 = {0, 0, 0, 0};
-    if (o0 != kNone) c0 = *reinterpret_cast<const uint4*>(base + (o0 * 64u + chunk));
-    if (o1 != kNone) c1 = *reinterpret_cast<const uint4*>(base + (o1 * 64u + chunk));
-    if (o2 != kNone) c2 = *reinterpret_cast<const uint4*>(base + (o2 * 64u + chunk));
-    if (o3 != kNone) c3 = *reinterpret_cast<const uint4*>(base + (o3 * 64u + chunk));
+__device__ inline void coop_load_pair(const PairNode<float>* pairs, uint32_t pair_bytes, uint32_t want, int lane, float (&lb)[6], float (&rb)[6], uint32_t& li, uint32_t& ri) {
+    // byte offset of the wanted record (kNoRecordAt for none), broadcast from quad lane k and combined with this lane's chunk in one
+    // DPP instruction per load (uniform base + 32-bit offset: the tree has fewer than 2^26 records)
+    const uint32_t at = want << 6, chunk = (static_cast<uint32_t>(lane) & 3u) * 16u;
+    const PairRsrc r = pair_rsrc(pairs, pair_bytes);
+    const uint4 c0 = load_chunk(r, quad_perm<0x00>(at) | chunk), c1 = load_chunk(r, quad_perm<0x55>(at) | chunk);
+    const uint4 c2 = load_chunk(r, quad_perm<0xAA>(at) | chunk), c3 = load_chunk(r, quad_perm<0xFF>(at) | chunk);
     uint32_t v0[4] = {c0.x, c0.y, c0.z, c0.w}, v1[4] = {c1.x, c1.y, c1.z, c1.w}, v2[4] = {c2.x, c2.y, c2.z, c2.w}, v3[4] = {c3.x, c3.y, c3.z, c3.w};
     // v_k[lane j] = chunk j of the record of quad lane k  ->  v_k[lane j] = chunk k of the record of quad lane j
     quad_exchange4<false>(v0, v1); quad_exchange4<false>(v2, v3);
@@ -221,7 +241,7 @@ __device__ inline void coop_load_pair(const PairNode<float>* pairs, uint32_t wan
 // quad's four lanes load the four 16-byte chunks of the first / second half of the record wanted by its lane k — two quad-coalesced
 // requests per record instead of a lane's eight — and two 4 x 4 transposes hand every lane its own 128 bytes:
 // first half = lb[0..5], rb[0..1]; second half = rb[2..5], {li, ri}, padding (common.h: PairNode<double>).
-__device__ inline void coop_load_pair(const PairNode<double>* pairs, uint32_t want, int lane, double (&lb)[6], double (&rb)[6], uint32_t& li, uint32_t& ri) {
+__device__ inline void coop_load_pair(const PairNode<double>* pairs, uint32_t, uint32_t want, int lane, double (&lb)[6], double (&rb)[6], uint32_t& li, uint32_t& ri) {
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     const uint32_t j = static_cast<uint32_t>(lane) & 3u;
     const uint32_t o0 = quad_perm<0x00>(want), o1 = quad_perm<0x55>(want), o2 = quad_perm<0xAA>(want), o3 = quad_perm<0xFF>(want);
@@ -246,7 +266,7 @@ __device__ inline void coop_load_pair(const PairNode<double>* pairs, uint32_t wa
     (void)w3;
 }
 #else
-template <typename T> inline void coop_load_pair(const PairNode<T>* p, uint32_t want, int, T (&lb)[6], T (&rb)[6], uint32_t& li, uint32_t& ri) {
+template <typename T> inline void coop_load_pair(const PairNode<T>* p, uint32_t, uint32_t want, int, T (&lb)[6], T (&rb)[6], uint32_t& li, uint32_t& ri) {
     if (want != 0xFFFFFFFFu) load_pair(p + want, lb, rb, li, ri);          // host harness: one emulated lane has no quad
 }
 #endif

@@ -754,6 +754,7 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
     }
     TraceArgs<T> args{};
     args.pairs = b.d_pairs; args.prims = d_prims; args.rays = d_rays; args.hits = d_hits;
+    args.pair_bytes = static_cast<uint32_t>(std::min<size_t>(b.pair_count * sizeof(PairNode<T>), 0xFFFFFFFFu));   // (exact for every tree launch_variant gives the cooperative kernels)
     args.n = n; args.work = work; args.counters = d_counters; args.root_index = b.root_index;
     args.order = nullptr;
     args.prim_stride = leaf_kind == LEAF_TRIANGLE ? (t_exp.tri_stride > 0 ? static_cast<uint32_t>(t_exp.tri_stride) : 12u) : 4u;
