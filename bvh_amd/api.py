@@ -468,6 +468,50 @@ def intersect(bvh: Bvh, prims, rays, any_hit: bool = False, robust: bool = False
     return out
 
 
+def closest_points(bvh: Bvh, prims, points, max_distance: float = float("inf"), leaf: str = "tri", counters: bool = False, out=None,
+                   sort_queries=None, original_ids: bool = False):
+    """For each point, the nearest primitive within max_distance and its distance (bvhXX_closest_points_*). prims are in BVH order
+    ((n, 12) PrecomputedTri or (n, 4) spheres, as for intersect). points: (n, 3) with the scalar max_distance, or (n, 4) with a
+    per-query radius in column 3 (max_distance left at its default). Returns the (n, 4) tensor of hit records (hits_to_numpy views
+    it): prim = BVH-order index (bvh.prim_ids[i] with original_ids) or INVALID, t = distance (max_distance on a miss), (u, v) the
+    barycentrics of the closest point of a triangle (point = p0 + u (p1 - p0) + v (p2 - p0); 0 for spheres); with counters also
+    (pairs, tests, leaves). sort_queries: True / False force / forbid reordering the batch internally (None: the library decides)."""
+    torch = _torch()
+    if bvh.dim != 3:
+        raise TypeError("closest_points: 3D trees only")
+    if leaf not in ("tri", "sphere"):
+        raise ValueError("leaf is 'tri' or 'sphere'")
+    s = bvh._s
+    dt = torch.float32 if s[1] == "f" else torch.float64
+    pts = _dev(points)
+    if pts.dim() != 2 or pts.shape[1] not in (3, 4):
+        raise ValueError("points must be (n, 3) or (n, 4)")
+    if pts.dtype != dt:
+        raise TypeError("points dtype must match the BVH scalar type")
+    if pts.shape[1] == 3:
+        q = torch.empty((pts.shape[0], 4), dtype=dt, device=pts.device)
+        q[:, :3] = pts
+        q[:, 3] = float(max_distance)
+    else:
+        if max_distance != float("inf"):
+            raise ValueError("(n, 4) points carry their own radius: leave max_distance at its default")
+        q = pts
+    p = _dev(prims)
+    if p.dtype != dt:
+        raise TypeError("prims dtype must match the BVH scalar type")
+    n = q.shape[0]
+    if out is None:
+        out = torch.empty((n, 4), dtype=dt, device=q.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    flags = (0 if sort_queries is None else RayFlags.SORTED if sort_queries else RayFlags.UNSORTED) | (8 if original_ids else 0)
+    fn = getattr(_lib.load(), f"bvh{s}_closest_points_{leaf}")
+    _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, int(flags), out.data_ptr(), cnt.data_ptr() if counters else None, _stream()),
+               "closest_points")
+    if counters:
+        return out, cnt
+    return out
+
+
 def hits_to_numpy(hits) -> np.ndarray:
     a = hits.detach().cpu().numpy()
     return a.view(HITF if a.dtype == np.float32 else HITD).reshape(-1)

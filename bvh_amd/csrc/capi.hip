@@ -466,6 +466,18 @@ int intersect(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, co
                               static_cast<hipStream_t>(stream));
 }
 
+template <typename T>
+int closest(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned flags,
+            typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, void* stream)
+{
+    if (!bvh) return fail(BVH_AMD_ERR_ARG, "closest_points: null bvh");
+    const BvhImpl<T>& b = *impl<T>(bvh);
+    int cur = -1;
+    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
+    if (n != 0 && cur != b.device) return fail(BVH_AMD_ERR_ARG, "closest_points: BVH lives on another device than the current one");
+    return launch_closest<T>(b, leaf, d_prims, d_queries4, n, flags, d_hits, d_counters, static_cast<hipStream_t>(stream));
+}
+
 // bvhXX_intersect_ray{,_any}{,_robust} (c_api/bvh.h:277-295 over bvh_impl.h:235-250): one ray, the leaves go to the caller's
 // function. The walk runs on the device (traverse.hip, ray_step_kernel); `ray` is the family's own struct.
 template <typename T, int D>
@@ -677,6 +689,12 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_intersect_rays_sphere(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, unsigned flags, \
                                        bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                          \
         return intersect<T>(b, LEAF_SPHERE, prims, rays, n, flags, hits, cnt, s); }                                 \
+    int bvh##S##_closest_points_tri(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned flags,       \
+                                    bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                             \
+        return closest<T>(b, LEAF_TRIANGLE, prims, queries, n, flags, hits, cnt, s); }                              \
+    int bvh##S##_closest_points_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned flags,    \
+                                       bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                          \
+        return closest<T>(b, LEAF_SPHERE, prims, queries, n, flags, hits, cnt, s); }                                \
     int bvh##S##_prepare_trace(const bvh##S* b, size_t n_rays_hint, void* s) {                                      \
         if (!b) return fail(BVH_AMD_ERR_ARG, "prepare_trace: null bvh");                                            \
         int cur = -1;                                                                                               \

@@ -249,6 +249,10 @@ template <typename T> int validate_resident_nodes(const HostNode<T>* d_nodes, si
 template <typename T>
 int launch_traverse(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T* d_rays, size_t n, unsigned flags,
                     typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, hipStream_t stream);
+// closest.hip: batched closest-point queries, n x {x, y, z, max_distance} -> one hit record each (flags: ORIGINAL_IDS, SORTED, UNSORTED)
+template <typename T>
+int launch_closest(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T* d_queries, size_t n, unsigned flags,
+                   typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, hipStream_t stream);
 void last_launch_plan(int out[4]);                            // traverse.hip: {reordered, coop, refill, leaf} of the calling thread's latest launch
 int wave_times(unsigned long long* out, size_t capacity_waves, size_t* n_waves);   // traverse.hip: developer library only
 void last_plan_search(float ns_per_ray[5], int measurements[5], unsigned* dropped);   // traverse.hip

@@ -281,6 +281,32 @@ def rays_shadow(n: int, lo, hi, seed: int = 4321, dtype=np.float32) -> np.ndarra
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# Query points (closest_points): (n, 3) = {x, y, z}
+# ----------------------------------------------------------------------------------------------
+
+def points_uniform(n: int, lo, hi, seed: int = 2468, scale: float = 1.1, dtype=np.float32) -> np.ndarray:
+    """Points uniform in the bbox scaled `scale`x about its centre."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    ctr, half = 0.5 * (lo + hi), 0.5 * (hi - lo) * scale
+    u = uniform01(seed, 3 * n, 0).reshape(n, 3)
+    return (ctr + (2.0 * u - 1.0) * half).astype(dtype)
+
+
+def points_near_surface(tris: np.ndarray, n: int, seed: int = 1357, sigma: float = 0.01) -> np.ndarray:
+    """A random triangle of `tris` (n, 9), a uniformly random point on it, plus an isotropic offset of standard deviation sigma per
+    axis (Box-Muller); the dtype of `tris`."""
+    t = np.asarray(tris).reshape(-1, 3, 3).astype(np.float64)
+    pick = (splitmix64(seed, n, 0) % np.uint64(len(t))).astype(np.int64)
+    w = uniform01(seed, 2 * n, 1).reshape(n, 2)
+    r1 = np.sqrt(w[:, 0:1])
+    a, b, c = t[pick, 0], t[pick, 1], t[pick, 2]
+    p = (1.0 - r1) * a + (r1 * (1.0 - w[:, 1:2])) * b + (r1 * w[:, 1:2]) * c
+    g = uniform01(seed, 6 * n, 2).reshape(n, 3, 2)
+    radius = np.sqrt(-2.0 * np.log(1.0 - g[..., 0]))
+    return (p + sigma * radius * np.cos(2.0 * np.pi * g[..., 1])).astype(np.asarray(tris).dtype)
+
+
 def rays_pinhole(width: int, height: int, eye, direction, up, dtype=np.float32) -> np.ndarray:
     """Primary rays of the reference's benchmark camera (test/benchmark.cpp:343-359): no fov term,
     ``dir + u * right + v * up`` with u = 2x/w - 1, v = 2y/h - 1, all in float32, row-major (y, x)."""

@@ -313,6 +313,8 @@ template <> struct Api<float, 3> {
     static int precompute(const void* t9, const uint32_t* perm, size_t n, void* out) { return bvh_amd_precompute_tris3f(static_cast<const float*>(t9), perm, n, static_cast<float*>(out), nullptr); }
     static int trace_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3f_intersect_rays_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int trace_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3f_intersect_rays_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
+    static int closest_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3f_closest_points_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
+    static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3f_closest_points_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, float*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitorf v{ user, leaf, inner };
         return bvh3f_intersect_ray_visit(h, static_cast<const bvh_ray3f*>(ray), start, f, &v);
@@ -342,6 +344,8 @@ template <> struct Api<double, 3> {
     static int precompute(const void* t9, const uint32_t* perm, size_t n, void* out) { return bvh_amd_precompute_tris3d(static_cast<const double*>(t9), perm, n, static_cast<double*>(out), nullptr); }
     static int trace_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3d_intersect_rays_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int trace_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3d_intersect_rays_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
+    static int closest_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3d_closest_points_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
+    static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3d_closest_points_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, double*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitord v{ user, leaf, inner };
         return bvh3d_intersect_ray_visit(h, static_cast<const bvh_ray3d*>(ray), start, f, &v);
@@ -402,6 +406,9 @@ template <typename T> struct Hit;
 template <> struct Hit<float>  { uint32_t prim; float t, u, v; static constexpr uint32_t invalid = BVH_AMD_INVALID; };
 template <> struct Hit<double> { uint32_t prim; uint32_t pad; double t, u, v; static constexpr uint32_t invalid = BVH_AMD_INVALID; };
 static_assert(sizeof(Hit<float>) == sizeof(bvh_hit3f) && sizeof(Hit<double>) == sizeof(bvh_hit3d));
+
+// One closest-point query (bvhXX_closest_points_*): the point and the largest distance of interest (+inf: unbounded).
+template <typename T> struct PointQuery { Vec<T, 3> p; T max_distance; };
 
 } // namespace amd
 
@@ -806,6 +813,39 @@ void intersect_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Nod
     DeviceArray<Ray<T, Node::dimension>> d_rays(rays);
     DeviceArray<Hit<T>> d_hits(rays.size());
     check(Api<T, Node::dimension>::trace_sphere(bvh.device(), spheres.data(), d_rays.data(), rays.size(), flags, d_hits.data()), "intersect_rays_sphere");
+    d_hits.download(hits);
+}
+
+// For each query, the nearest primitive within its max_distance (include/bvh_amd.h: bvhXX_closest_points_*): hit.prim = BVH-order
+// index (invalid on a miss, t = max_distance then), hit.t = distance, (u, v) = barycentrics of a triangle's closest point (0 for spheres).
+template <typename Node>
+void closest_points_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims,
+                          const DeviceArray<PointQuery<typename Node::Scalar>>& queries, DeviceArray<Hit<typename Node::Scalar>>& hits) {
+    using T = typename Node::Scalar;
+    check(Api<T, 3>::closest_tri(bvh.device(), prims.data(), queries.data(), queries.size(), 0u, hits.data()), "closest_points_tri");
+}
+template <typename Node>
+void closest_points_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims,
+                          std::span<const PointQuery<typename Node::Scalar>> queries, std::span<Hit<typename Node::Scalar>> hits) {
+    using T = typename Node::Scalar;
+    DeviceArray<PointQuery<T>> d_queries(queries);
+    DeviceArray<Hit<T>> d_hits(queries.size());
+    closest_points_batch(bvh, prims, d_queries, d_hits);
+    d_hits.download(hits);
+}
+template <typename Node>
+void closest_points_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres,
+                          const DeviceArray<PointQuery<typename Node::Scalar>>& queries, DeviceArray<Hit<typename Node::Scalar>>& hits) {
+    using T = typename Node::Scalar;
+    check(Api<T, 3>::closest_sphere(bvh.device(), spheres.data(), queries.data(), queries.size(), 0u, hits.data()), "closest_points_sphere");
+}
+template <typename Node>
+void closest_points_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres,
+                          std::span<const PointQuery<typename Node::Scalar>> queries, std::span<Hit<typename Node::Scalar>> hits) {
+    using T = typename Node::Scalar;
+    DeviceArray<PointQuery<T>> d_queries(queries);
+    DeviceArray<Hit<T>> d_hits(queries.size());
+    closest_points_batch(bvh, spheres, d_queries, d_hits);
     d_hits.download(hits);
 }
 

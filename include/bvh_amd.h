@@ -117,6 +117,7 @@ enum bvh_amd_ray_flags {
                                   whose node records exceed the 32 MB of L2 and through which a random line is expected to fetch
                                   >= 100 records (sum of area(node) / area(root) over the inner nodes): +40..50 % there      */
     BVH_AMD_RAY_UNSORTED = 16u, /* never reorder (rays already coherent, or no scratch memory to spare: 16 bytes per ray)  */
+                                /* (SORTED / UNSORTED / ORIGINAL_IDS apply to bvhXX_closest_points_* queries too) */
     BVH_AMD_RAY_ORIGINAL_IDS = 8u  /* hit.prim = the ORIGINAL primitive id bvh.prim_ids[i] (what c_api_example.c:265-268 looks up per
                                       hit) instead of the BVH-order index i: one more pass over the hit records, on the device    */
 };
@@ -429,6 +430,28 @@ BVH_AMD_API int bvh3f_intersect_rays_sphere(const struct bvh3f*, const float* d_
     size_t n, unsigned flags, struct bvh_hit3f* d_hits, struct bvh_amd_counters* d_counters, void* stream);
 BVH_AMD_API int bvh3d_intersect_rays_sphere(const struct bvh3d*, const double* d_sph4, const struct bvh_ray3d* d_rays,
     size_t n, unsigned flags, struct bvh_hit3d* d_hits, struct bvh_amd_counters* d_counters, void* stream);
+
+/* ---- batched closest-point queries: for each point, the nearest primitive and its distance ------------------------------- */
+/* d_queries4 holds n x {x, y, z, max_distance} of the tree's scalar type (16 B per query for 3f, 32 B for 3d); d_prims are the
+ * BVH-order PrecomputedTri (tri) or Sphere<T, 3> {c, r} (sphere) arrays that bvhXX_intersect_rays_* take. One record per query:
+ *   hit:  prim = the BVH-order index (bvh.prim_ids[i] with BVH_AMD_RAY_ORIGINAL_IDS) of the primitive at the smallest squared
+ *         distance <= max_distance^2, ties to the lowest index; t = sqrt(d^2). Triangles: distance to the solid triangle, (u, v) the
+ *         barycentrics of its closest point, point = p0 + u (p1 - p0) + v (p2 - p0). Spheres: max(|q - c| - r, 0), u = v = 0.
+ *   miss: prim = BVH_AMD_INVALID, t = max_distance, u = v = 0 (also for a NaN coordinate and a negative or NaN max_distance;
+ *         +inf = unbounded).
+ * flags: BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED (reorder the batch by the Hilbert cell of each point in the
+ * root box, or never; with neither the library reorders batches of >= 1M queries). Any other bit: BVH_AMD_ERR_ARG. A record depends
+ * only on the tree, the primitives and its query (not on batch size, position or order). n == 0 is a no-op. Device pointers must be
+ * 16-byte aligned; d_counters (optional) receives {pair records fetched, primitives tested, leaves visited}. 3D trees only.
+ * Re-entrant on a const tree, like bvhXX_intersect_rays_*. */
+BVH_AMD_API int bvh3f_closest_points_tri(const struct bvh3f*, const float* d_tris12, const float* d_queries4, size_t n, unsigned flags,
+    struct bvh_hit3f* d_out, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_closest_points_tri(const struct bvh3d*, const double* d_tris12, const double* d_queries4, size_t n, unsigned flags,
+    struct bvh_hit3d* d_out, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_closest_points_sphere(const struct bvh3f*, const float* d_sph4, const float* d_queries4, size_t n, unsigned flags,
+    struct bvh_hit3f* d_out, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_closest_points_sphere(const struct bvh3d*, const double* d_sph4, const double* d_queries4, size_t n, unsigned flags,
+    struct bvh_hit3d* d_out, struct bvh_amd_counters* d_counters, void* stream);
 
 /* Optional, additive: pays NOW what the first large batch through a fresh tree would pay inside its own call — the tree's depth /
  * expected-visits pass (one read-back) and the first allocation of the ray-reordering scratch for batches of `n_rays_hint` rays (kept

@@ -1,0 +1,57 @@
+// Closest-point queries through the C++20 mirror (bvh::v2::amd::closest_points_batch): a small deterministic mesh, serial High build,
+// permuted PrecomputedTri, a batch of queries with and without a radius. Prints the tree's prim ids, then one line per query
+// "prim t u v" (t, u, v as hexadecimal floats: exact); tests/test_gpu_closest_point.py compares them with bvh_amd.closest_points.
+#include <bvh/v2/bvh.h>
+#include <bvh/v2/vec.h>
+#include <bvh/v2/node.h>
+#include <bvh/v2/default_builder.h>
+#include <bvh/v2/tri.h>
+
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+using Scalar = float;
+using Vec3 = bvh::v2::Vec<Scalar, 3>;
+using BBox = bvh::v2::BBox<Scalar, 3>;
+using Tri = bvh::v2::Tri<Scalar, 3>;
+using Node = bvh::v2::Node<Scalar, 3>;
+using Bvh = bvh::v2::Bvh<Node>;
+using Hit = bvh::v2::amd::Hit<Scalar>;
+using Query = bvh::v2::amd::PointQuery<Scalar>;
+static_assert(sizeof(Query) == 4 * sizeof(Scalar));
+
+int main() {
+    std::vector<Tri> tris;                                    // a 12 x 12 height field, two triangles per cell
+    const int side = 12;
+    auto h = [](int i, int j) { return static_cast<Scalar>(0.1 * std::sin(0.7 * i) * std::cos(0.4 * j)); };
+    for (int i = 0; i < side; ++i)
+        for (int j = 0; j < side; ++j) {
+            const Vec3 a(Scalar(i), h(i, j), Scalar(j)), b(Scalar(i + 1), h(i + 1, j), Scalar(j));
+            const Vec3 c(Scalar(i + 1), h(i + 1, j + 1), Scalar(j + 1)), d(Scalar(i), h(i, j + 1), Scalar(j + 1));
+            tris.emplace_back(a, b, c);
+            tris.emplace_back(a, c, d);
+        }
+    std::vector<BBox> bboxes(tris.size());
+    std::vector<Vec3> centers(tris.size());
+    for (size_t i = 0; i < tris.size(); ++i) { bboxes[i] = tris[i].get_bbox(); centers[i] = tris[i].get_center(); }
+    typename bvh::v2::DefaultBuilder<Node>::Config config;
+    config.quality = bvh::v2::DefaultBuilder<Node>::Quality::High;
+    auto bvh = bvh::v2::DefaultBuilder<Node>::build(bboxes, centers, config);
+    auto prims = bvh::v2::amd::permuted_triangles(bvh, std::span<const Tri>(tris));
+
+    std::vector<Query> queries;
+    for (int k = 0; k < 200; ++k) {
+        const Scalar x = Scalar(-1.5 + 15.0 * ((k * 37) % 200) / 200.0), y = Scalar(-1.0 + 2.0 * ((k * 53) % 200) / 200.0);
+        const Scalar z = Scalar(-1.5 + 15.0 * ((k * 91) % 200) / 200.0);
+        queries.push_back(Query{ Vec3(x, y, z), k % 2 ? Scalar(0.25) : Scalar(INFINITY) });
+    }
+    std::vector<Hit> hits(queries.size());
+    bvh::v2::amd::closest_points_batch(bvh, prims, std::span<const Query>(queries), std::span<Hit>(hits));
+
+    std::printf("prim_ids:");
+    for (size_t id : bvh.prim_ids) std::printf(" %zu", id);
+    std::printf("\n");
+    for (const Hit& hit : hits) std::printf("%u %a %a %a\n", hit.prim, double(hit.t), double(hit.u), double(hit.v));
+    return 0;
+}
