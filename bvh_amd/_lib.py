@@ -114,6 +114,9 @@ _SIGS_T = {
     "bvh{S}_refit": (None, [_P]),
     "bvh{S}_refit_status": (_I, [_P]),
     "bvh{S}_sync_device": (_I, [_P]),
+    "bvh{S}_refit_boxes": (_I, [_P, _P, _Z, _P]),
+    "bvh{S}_refit_tris": (_I, [_P, _P, _Z, _P, _P]),
+    "bvh{S}_traversal_cost": (_I, [_P, C.POINTER(C.c_double), _P]),
     "bvh{S}_append_node": (None, [_P]),
     "bvh{S}_remove_last_node": (None, [_P]),
     "bvh_node{S}_set_prim_count": (None, [_P, _Z]),
@@ -179,7 +182,8 @@ def ray_visitor_types(suffix: str):
 
 _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_intersect_rays_tri", "bvh{S}_prepare_trace",     # tri.h is 3D only,
             "bvh{S}_build_minitree_device",                                                           # and so is the mini-tree grid
-            "bvh{S}_closest_points_tri", "bvh{S}_closest_points_sphere")                              # and the closest-point queries
+            "bvh{S}_closest_points_tri", "bvh{S}_closest_points_sphere",                              # and the closest-point queries
+            "bvh{S}_refit_tris", "bvh{S}_traversal_cost")                                             # (tri.h; the 3D area term)
 
 
 def exported_symbols():

@@ -176,6 +176,46 @@ class Bvh:
         _torch()
         _lib.check(self._f("bvh{S}_refit_status")(self._h), "refit")
 
+    def _prims_in(self, x, cols, what):
+        torch = _torch()
+        if not hasattr(x, "dtype"):
+            x = np.asarray(x)
+        dt = x.dtype
+        want = torch.float32 if self._s[1] == "f" else torch.float64
+        if dt not in (want, np.dtype(self.dtype), self.dtype):
+            raise TypeError(f"{what}: the tree is {np.dtype(self.dtype).name}, the array is {dt}")
+        return _dev(x, cols)
+
+    def refit_boxes(self, bboxes):
+        """Leaf boxes from `bboxes` ((n, 2 dim) {min, max}, indexed by ORIGINAL primitive id, numpy or torch), inner boxes bottom-up;
+        nodes and traversal records updated in place on the current torch stream, no host copy (bvhXX_refit_boxes)."""
+        bb = self._prims_in(bboxes, 2 * self.dim, "refit_boxes")
+        _lib.check(self._f("bvh{S}_refit_boxes")(self._h, bb.data_ptr(), bb.shape[0], _stream()), "refit_boxes")
+
+    def refit_tris(self, tris9, out=None):
+        """refit_boxes with Tri::get_bbox of (n, 9) triangles in original order, and the BVH-order PrecomputedTri array ((prim_count, 12),
+        written into `out` if given) that intersect / closest_points take: deformed vertices to a traceable pair in one call."""
+        torch = _torch()
+        if self.dim != 3:
+            raise TypeError("refit_tris: triangles are 3D (tri.h)")
+        t = self._prims_in(tris9, 9, "refit_tris")
+        if out is None:
+            out = torch.empty((self.prim_count, 12), dtype=t.dtype, device=t.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == t.dtype and out.numel() == 12 * self.prim_count):
+            raise TypeError("refit_tris: `out` must be a contiguous (prim_count, 12) device tensor of the tree's scalar type")
+        _lib.check(self._f("bvh{S}_refit_tris")(self._h, t.data_ptr(), t.shape[0], out.data_ptr(), _stream()), "refit_tris")
+        return out.reshape(-1, 12)
+
+    def traversal_cost(self) -> float:
+        """Traversal records a random line through the scene is expected to fetch, from the current boxes (bvh3X_traversal_cost): grows
+        as a refitted tree degrades. Synchronises the current stream."""
+        _torch()
+        if self.dim != 3:
+            raise TypeError("traversal_cost: 3D trees only")
+        cost = C.c_double(0.0)
+        _lib.check(self._f("bvh{S}_traversal_cost")(self._h, C.byref(cost), _stream()), "traversal_cost")
+        return float(cost.value)
+
     def set_node_bbox(self, node_id: int, lo, hi):
         """bvh_nodeXX_set_bbox on the host mirror (takes effect on the device at the next refit()/sync_device())."""
         node = self._f("bvh{S}_get_node")(self._h, node_id)

@@ -249,7 +249,9 @@ template <typename T, typename Op>
 int on_resident_nodes(BvhImpl<T>* pb, Op op) {
     if (!pb) return fail(BVH_AMD_ERR_ARG, "null bvh");
     BvhImpl<T>& b = *pb;
-    int rc = make_nodes_resident<T>(b);
+    int rc = b.wait_refit();                                   // (a pending root refresh of refit_boxes / refit_tris must not overwrite the one below)
+    if (rc) return rc;
+    rc = make_nodes_resident<T>(b);
     if (rc) return rc;
     const size_t bytes = b.node_count * sizeof(HostNode<T>);
     rc = op(b.d_nodes, b.node_count);
@@ -306,6 +308,61 @@ template <typename T> int optimize_config(BvhImpl<T>* b, const bvh_amd_optimize_
 }
 template <typename T> int refit(BvhImpl<T>* b) {
     return on_resident_nodes<T>(b, [](HostNode<T>* d, size_t n) { return refit_device<T>(d, n, nullptr); });
+}
+
+// bvhXX_refit_boxes / bvh3X_refit_tris: leaf boxes from primitives in HBM, inner boxes bottom-up, reference-layout nodes and traversal
+// records updated in place on the caller's stream (refit_prims.hip). What depends on the topology only — max_depth, the measured
+// launch plan, d_prim_ids, the work slots — is kept; the host mirror is marked stale and refilled lazily by sync_host().
+// One-offs, not paid per frame: the largest prim id (one read-back, cached per tree), and, when the mirror holds the only or a
+// possibly edited copy of the nodes (host_valid), the push + validation + re-layout that bvhXX_refit does on every call.
+template <typename T>
+int refit_prims(BvhImpl<T>* pb, int src_kind, const T* d_src, size_t n_src, T* d_tris12_out, void* stream_, const char* who) {
+    if (!pb) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": null bvh");
+    if (!d_src) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": null primitive array");
+    BvhImpl<T>& b = *pb;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int cur = -1;
+    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
+    if (cur != b.device) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH lives on another device than the current one");
+    if (b.node_count == 0 || !b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH has no device copy");
+    if (b.max_prim_id < 0) {
+        uint32_t largest = 0;
+        const int rc = max_prim_id_device(b.d_prim_ids, b.prim_count, stream, &largest);
+        if (rc) return rc;
+        b.max_prim_id = largest;
+    }
+    if (b.prim_count && n_src <= static_cast<size_t>(b.max_prim_id))
+        return fail(BVH_AMD_ERR_ARG, std::string(who) + ": " + std::to_string(n_src) + " primitives given, but prim_ids refers to primitive " +
+                    std::to_string(b.max_prim_id) + " (the array is indexed by original primitive id)");
+    // (no wait for an earlier refit_*'s root copy here: note_refit() below supersedes it, and the host blocks on nothing in the steady
+    //  state; the mirror can only be valid after sync_host(), which has waited)
+    const bool from_host = b.host_valid || !b.d_nodes || b.d_nodes_count != b.node_count;
+    int rc = from_host ? b.wait_refit() : BVH_AMD_OK;
+    if (rc) return rc;
+    rc = make_nodes_resident<T>(b);
+    if (rc) return rc;
+    if (from_host || (b.pair_count && !b.d_pairs)) {           // index words may have been edited: the records are rebuilt (and the plan with them)
+        const long long largest = b.max_prim_id;
+        rc = relayout_on_device<T>(b, b.d_nodes, stream);
+        if (rc) return rc;
+        b.max_prim_id = largest;                               // (prim_ids cannot be edited through the mirror)
+    }
+    rc = refit_prims_device<T>(b.d_nodes, b.d_pairs, b.node_count, src_kind, d_src, n_src, b.d_prim_ids, b.prim_count, stream);
+    if (rc == BVH_AMD_OK && d_tris12_out) rc = launch_precompute_tris<T>(d_src, b.d_prim_ids, b.prim_count, d_tris12_out, stream);
+    // the boxes on the device are ahead of the mirror from here on, also after a failed launch
+    b.host_valid = false;
+    b.nodes2_valid = false;
+    const int rc2 = b.note_refit(stream);
+    return rc ? rc : rc2;
+}
+
+template <typename T>
+int traversal_cost_checked(const BvhImpl<T>* b, double* cost_out, void* stream) {
+    if (!b || !cost_out) return fail(BVH_AMD_ERR_ARG, "traversal_cost: null bvh or output");
+    int cur = -1;
+    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
+    if (cur != b->device) return fail(BVH_AMD_ERR_ARG, "traversal_cost: BVH lives on another device than the current one");
+    return traversal_cost<T>(*b, cost_out, static_cast<hipStream_t>(stream));
 }
 
 // Host-side edits (bvh_node* setters, append/remove) live in the mirror; this pushes them to the device copy.
@@ -632,6 +689,11 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     void bvh##S##_refit(bvh##S* b) { loud_or_abort(refit<T>(impl<T>(b)), "bvh" #S "_refit"); }                     \
     int bvh##S##_refit_status(bvh##S* b) { return refit<T>(impl<T>(b)); }                                           \
     int bvh##S##_sync_device(bvh##S* b) { return sync_device<T>(impl<T>(b)); }                                       \
+    int bvh##S##_refit_boxes(bvh##S* b, const T* d_bb, size_t n, void* s) {                                         \
+        return refit_prims<T>(impl<T>(b), REFIT_BOXES3, d_bb, n, nullptr, s, "refit_boxes"); }                       \
+    int bvh##S##_refit_tris(bvh##S* b, const T* d_tris9, size_t n, T* d_tris12_out, void* s) {                      \
+        return refit_prims<T>(impl<T>(b), REFIT_TRIS, d_tris9, n, d_tris12_out, s, "refit_tris"); }                  \
+    int bvh##S##_traversal_cost(bvh##S* b, double* cost_out, void* s) { return traversal_cost_checked<T>(impl<T>(b), cost_out, s); } \
     void bvh##S##_append_node(bvh##S* b) {                                                                          \
         if (impl<T>(b)->sync_host() != BVH_AMD_OK) return;                                                           \
         impl<T>(b)->nodes.emplace_back(); impl<T>(b)->node_count = impl<T>(b)->nodes.size(); }                       \
@@ -744,6 +806,8 @@ BVH_AMD_IMPL_RAY(double, 3d, bvh_intersect_callbackd, bvh_amd_ray_visitord, 3, i
     void bvh##S##_refit(bvh##S* b) { loud_or_abort(refit<T>(impl2<T>(b)), "bvh" #S "_refit"); }                    \
     int bvh##S##_refit_status(bvh##S* b) { return refit<T>(impl2<T>(b)); }                                          \
     int bvh##S##_sync_device(bvh##S* b) { return sync_device<T>(impl2<T>(b)); }                                      \
+    int bvh##S##_refit_boxes(bvh##S* b, const T* d_bb4, size_t n, void* s) {                                        \
+        return refit_prims<T>(impl2<T>(b), REFIT_BOXES2, d_bb4, n, nullptr, s, "refit_boxes"); }                     \
     void bvh##S##_append_node(bvh##S* b) {                                                                          \
         if (impl2<T>(b)->sync_host2() != BVH_AMD_OK) return;                                                         \
         impl2<T>(b)->nodes2.emplace_back(); impl2<T>(b)->node_count = impl2<T>(b)->nodes2.size(); }                  \

@@ -161,6 +161,7 @@ int launch_closest(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T
         static const int cell_bits = std::max(1, std::min(8, BVH_DEV_INT("BVH_AMD_CLOSEST_KEY_BITS", 7)));       // developer knob
         const uint32_t cells = 1u << cell_bits;
         T lo[3], sc[3];
+        if (const int rc0 = b.wait_refit()) return release(rc0);      // root_bounds follows a refit_* that changed the boxes on the device
         for (int k = 0; k < 3; ++k) {
             const T ext = b.root_bounds[2 * k + 1] - b.root_bounds[2 * k];
             lo[k] = b.root_bounds[2 * k];

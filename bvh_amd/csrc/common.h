@@ -105,8 +105,18 @@ struct BvhImpl {
     void widen_host() const;                   // nodes2 -> nodes (z = 0): the caller may have edited nodes2 through bvh_node2X pointers
     HostNode<T>* d_nodes = nullptr;            // reference-layout nodes resident in HBM (device builds)
     size_t d_nodes_count = 0;                  // its capacity in nodes (append/remove_last_node change node_count on the host)
-    T root_bounds[6] = {0, 0, 0, 0, 0, 0};
+    mutable T root_bounds[6] = {0, 0, 0, 0, 0, 0};     // HOST copy of the root's box: scales the reordering keys (speed only, never results)
     int sync_host() const;
+    // bvhXX_refit_boxes / bvh3X_refit_tris change the boxes on the device without a synchronisation: each call ends with an async
+    // copy of the root node into the pinned slot `h_root` and records `refit_done` behind it. Whoever reads root_bounds or copies
+    // d_nodes to the host calls wait_refit() first: it waits for the event (normally long complete) and refreshes root_bounds.
+    HostNode<T>* h_root = nullptr;
+    hipEvent_t refit_done = nullptr;
+    mutable std::atomic<bool> root_pending{false};
+    mutable std::mutex root_mutex;
+    int wait_refit() const;
+    int note_refit(hipStream_t stream);        // queues the root copy + event (creates both on first use)
+    long long max_prim_id = -1;                // largest value in d_prim_ids (-1: not computed yet; reset when the tree is re-laid out)
     // device copy
     int device = -1;
     PairNode<T>* d_pairs = nullptr;            // (node_count - 1) / 2 records
@@ -304,5 +314,13 @@ int build_on_device(BvhImpl<T>& out, const T* d_bboxes, const T* d_centers, size
                     bvh_amd_builder builder, hipStream_t stream);
 
 enum { LEAF_TRIANGLE = 0, LEAF_SPHERE = 1 };
+
+// refit_prims.hip: where a leaf's boxes come from: n x {min, max} of 3 or 2 components, or n x {p0, p1, p2} (Tri::get_bbox, tri.h:24)
+enum { REFIT_BOXES3 = 0, REFIT_BOXES2 = 1, REFIT_TRIS = 2 };
+template <typename T>
+int refit_prims_device(HostNode<T>* d_nodes, PairNode<T>* d_pairs, size_t node_count, int src_kind, const T* d_src, size_t n_src,
+                       const uint32_t* d_prim_ids, size_t prim_count, hipStream_t stream);
+int max_prim_id_device(const uint32_t* d_prim_ids, size_t prim_count, hipStream_t stream, uint32_t* out);
+template <typename T> int traversal_cost(const BvhImpl<T>& b, double* cost_out, hipStream_t stream);   // upload.hip
 
 } // namespace bvh_amd

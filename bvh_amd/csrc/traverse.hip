@@ -797,6 +797,7 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
         const uint32_t n32 = static_cast<uint32_t>(n);
         uint32_t *keys = static_cast<uint32_t*>(sort_mem), *vals = keys + n, *kt = vals + n, *vt = kt + n, *hist = vt + n;
         T lo[3], sc[3];
+        if (const int rc0 = b.wait_refit()) return release(rc0);      // root_bounds follows a refit_* that changed the boxes on the device
         for (int k = 0; k < 3; ++k) {
             const T ext = b.root_bounds[2 * k + 1] - b.root_bounds[2 * k];
             lo[k] = b.root_bounds[2 * k];

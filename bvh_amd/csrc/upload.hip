@@ -88,6 +88,7 @@ int tree_depth(const BvhImpl<T>& b, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(once);
     if (b.max_depth.load() >= 0) return BVH_AMD_OK;
     if (b.pair_count == 0) { b.max_depth = 0; return BVH_AMD_OK; }
+    if (const int rc = b.wait_refit()) return rc;
     const uint32_t n = static_cast<uint32_t>(b.pair_count);
     // (round 5: from the scratch block cache like every other temporary — a plain hipMalloc + hipFree pair, the latter a device
     //  synchronisation, was a good part of what the FIRST batch through a fresh tree paid over a settled one)
@@ -151,13 +152,72 @@ BvhImpl<T>::~BvhImpl() {
         for (hipEvent_t& e : work_done) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         for (PlanSearch& ps : plan_search) { if (ps.start) (void)hipEventDestroy(ps.start); if (ps.stop) (void)hipEventDestroy(ps.stop); ps.start = ps.stop = nullptr; }
         if (d_nodes) { scratch_forget(d_nodes); (void)hipFree(d_nodes); }
+        if (refit_done) { (void)hipEventSynchronize(refit_done); (void)hipEventDestroy(refit_done); }
+        if (h_root) (void)hipHostFree(h_root);
         if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
     }
 }
 
+// The latest bvhXX_refit_boxes / bvh3X_refit_tris has run: its root box becomes the host's root_bounds.
+template <typename T>
+int BvhImpl<T>::wait_refit() const {
+    if (!root_pending.load(std::memory_order_acquire)) return BVH_AMD_OK;
+    std::lock_guard<std::mutex> lock(root_mutex);
+    if (!root_pending.load(std::memory_order_acquire)) return BVH_AMD_OK;
+    BVH_HIP_TRY(hipEventSynchronize(refit_done), BVH_AMD_ERR_HIP);
+    for (int k = 0; k < 6; ++k) root_bounds[k] = h_root->bounds[k];
+    root_pending.store(false, std::memory_order_release);
+    return BVH_AMD_OK;
+}
+
+template <typename T>
+int BvhImpl<T>::note_refit(hipStream_t stream) {
+    std::lock_guard<std::mutex> lock(root_mutex);
+    if (!h_root) BVH_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_root), sizeof(HostNode<T>), hipHostMallocDefault), BVH_AMD_ERR_HIP);
+    if (!refit_done) BVH_HIP_TRY(hipEventCreateWithFlags(&refit_done, hipEventDisableTiming), BVH_AMD_ERR_HIP);
+    BVH_HIP_TRY(hipMemcpyAsync(h_root, d_nodes, sizeof(HostNode<T>), hipMemcpyDeviceToHost, stream), BVH_AMD_ERR_HIP);
+    BVH_HIP_TRY(hipEventRecord(refit_done, stream), BVH_AMD_ERR_HIP);
+    root_pending.store(true, std::memory_order_release);
+    return BVH_AMD_OK;
+}
+
+// bvh3X_traversal_cost: k_expected_visits over the CURRENT records — one term per inner CHILD of a pair record, so every inner node
+// but the root (which is nobody's child) counts half_area(node) / half_area(root), truncated to units of 2^-16. One read-back.
+template <typename T>
+int traversal_cost(const BvhImpl<T>& b, double* cost_out, hipStream_t stream) {
+    int rc = b.wait_refit();
+    if (rc) return rc;
+    double cost = 0.0;
+    if (b.pair_count) {
+        StreamScope scratch_on(stream);
+        ScratchTag tag;
+        unsigned long long* d_sum = nullptr;
+        BVH_HIP_TRY(scratch_alloc(reinterpret_cast<void**>(&d_sum), 16, &tag), BVH_AMD_ERR_HIP);
+        const uint32_t n = static_cast<uint32_t>(b.pair_count);
+        const double x = double(b.root_bounds[1]) - double(b.root_bounds[0]), y = double(b.root_bounds[3]) - double(b.root_bounds[2]),
+                     z = double(b.root_bounds[5]) - double(b.root_bounds[4]);
+        const double area = x * y + y * z + z * x;
+        unsigned long long sum = 0;
+        hipError_t e = hipMemsetAsync(d_sum, 0, 8, stream);
+        hipLaunchKernelGGL(k_expected_visits<T>, dim3((n + 255) / 256), dim3(256), 0, stream, b.d_pairs, n, area > 0 ? 1.0 / area : 0.0, d_sum);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_sum, 8, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        scratch_free(d_sum, tag);
+        if (e != hipSuccess) return fail(BVH_AMD_ERR_HIP, std::string("traversal_cost: ") + hipGetErrorString(e));
+        cost = static_cast<double>(sum) / 65536.0;
+    }
+    b.expected_visits = static_cast<float>(cost);
+    *cost_out = cost;
+    return BVH_AMD_OK;
+}
+template int traversal_cost<float>(const BvhImpl<float>&, double*, hipStream_t);
+template int traversal_cost<double>(const BvhImpl<double>&, double*, hipStream_t);
+
 template <typename T>
 int BvhImpl<T>::sync_host() const {
     if (host_valid.load(std::memory_order_acquire)) return BVH_AMD_OK;
+    if (const int rc = wait_refit()) return rc;               // (a refit_* in flight on a non-blocking stream is not ordered before the copy below)
     std::lock_guard<std::mutex> lock(host_mutex);
     if (host_valid.load(std::memory_order_acquire)) return BVH_AMD_OK;
     int cur = -1;
@@ -179,6 +239,7 @@ template <typename T>
 int relayout_on_device(BvhImpl<T>& b, const HostNode<T>* d_nodes, hipStream_t stream) {
     b.pair_count = (b.node_count - 1) / 2;
     b.max_depth = -1;
+    b.max_prim_id = -1;
     { std::lock_guard<std::mutex> lock(b.plan_mutex); for (int k = 0; k < 2; ++k) { b.launch_plan[k] = 0; b.plan_search[k].index = 0; b.plan_search[k].pending = false; b.plan_search[k].trying = -1; b.plan_search[k].dropped = 0; for (auto& c : b.plan_search[k].count) c = 0; for (auto& t : b.plan_search[k].ns_per_ray) t = 0.0f; for (auto& r : b.plan_search[k].rays_of) r = 0; } }
     if (b.d_pairs) { scratch_forget(b.d_pairs); (void)hipFree(b.d_pairs); b.d_pairs = nullptr; }
     if (b.pair_count) {

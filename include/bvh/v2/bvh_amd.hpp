@@ -307,6 +307,9 @@ template <> struct Api<float, 3> {
     static void optimize(Handle* h) { bvh3f_optimize(nullptr, h); }
     static int optimize_config(Handle* h, const bvh_amd_optimize_config* c) { return bvh3f_optimize_config(h, c); }
     static void refit(Handle* h) { bvh3f_refit(h); }
+    static int refit_boxes(Handle* h, const void* d_bb, size_t n) { return bvh3f_refit_boxes(h, static_cast<const float*>(d_bb), n, nullptr); }
+    static int refit_tris(Handle* h, const void* d_t9, size_t n, void* d_out12) { return bvh3f_refit_tris(h, static_cast<const float*>(d_t9), n, static_cast<float*>(d_out12), nullptr); }
+    static int traversal_cost(Handle* h, double* out) { return bvh3f_traversal_cost(h, out, nullptr); }
     static const uint32_t* device_prim_ids(const Handle* h) { return bvh3f_device_prim_ids(h); }
     static Handle* broadcast(bvh_amd_comm* c, int root, Handle* h, const void* p, size_t bytes, void** p_out, size_t* bytes_out) { return bvh3f_broadcast(c, root, h, p, bytes, p_out, bytes_out, nullptr); }
     static int replicate(Handle* h, const void* p, size_t bytes, int n, const int* devs, Handle** out, void** p_out) { return bvh3f_replicate(h, p, bytes, n, devs, out, p_out); }
@@ -338,6 +341,9 @@ template <> struct Api<double, 3> {
     static void optimize(Handle* h) { bvh3d_optimize(nullptr, h); }
     static int optimize_config(Handle* h, const bvh_amd_optimize_config* c) { return bvh3d_optimize_config(h, c); }
     static void refit(Handle* h) { bvh3d_refit(h); }
+    static int refit_boxes(Handle* h, const void* d_bb, size_t n) { return bvh3d_refit_boxes(h, static_cast<const double*>(d_bb), n, nullptr); }
+    static int refit_tris(Handle* h, const void* d_t9, size_t n, void* d_out12) { return bvh3d_refit_tris(h, static_cast<const double*>(d_t9), n, static_cast<double*>(d_out12), nullptr); }
+    static int traversal_cost(Handle* h, double* out) { return bvh3d_traversal_cost(h, out, nullptr); }
     static const uint32_t* device_prim_ids(const Handle* h) { return bvh3d_device_prim_ids(h); }
     static Handle* broadcast(bvh_amd_comm* c, int root, Handle* h, const void* p, size_t bytes, void** p_out, size_t* bytes_out) { return bvh3d_broadcast(c, root, h, p, bytes, p_out, bytes_out, nullptr); }
     static int replicate(Handle* h, const void* p, size_t bytes, int n, const int* devs, Handle** out, void** p_out) { return bvh3d_replicate(h, p, bytes, n, devs, out, p_out); }
@@ -371,6 +377,7 @@ template <> struct Api<T, 2> {                                                  
     static void optimize(Handle* h) { bvh##S##_optimize(nullptr, h); }                                                                    \
     static int optimize_config(Handle* h, const bvh_amd_optimize_config* c) { return bvh##S##_optimize_config(h, c); }                    \
     static void refit(Handle* h) { bvh##S##_refit(h); }                                                                                   \
+    static int refit_boxes(Handle* h, const void* d_bb, size_t n) { return bvh##S##_refit_boxes(h, static_cast<const T*>(d_bb), n, nullptr); } \
     static const uint32_t* device_prim_ids(const Handle* h) { return bvh##S##_device_prim_ids(h); }                                       \
     static Handle* broadcast(bvh_amd_comm* c, int root, Handle* h, const void* p, size_t bytes, void** p_out, size_t* bytes_out) { return bvh##S##_broadcast(c, root, h, p, bytes, p_out, bytes_out, nullptr); } \
     static int replicate(Handle* h, const void* p, size_t bytes, int n, const int* devs, Handle** out, void** p_out) { return bvh##S##_replicate(h, p, bytes, n, devs, out, p_out); } \
@@ -562,6 +569,10 @@ struct Bvh {
         return device_.get();
     }
     void share(const Bvh& o) { nodes = o.nodes; prim_ids = o.prim_ids; device_ = o.device_; }     // the same device twin, one more owner
+    // host mirror -> device twin / device twin -> host mirror, for the free functions that run a device operation on this tree
+    // (amd::refit_boxes, amd::refit_tris): the public `nodes` must never be left stale
+    void sync_to_device() { push(); }
+    void sync_from_device() { pull(); }
     void adopt(typename amd::Api<Scalar, Node::dimension>::Handle* h) {
         device_ = std::shared_ptr<typename amd::Api<Scalar, Node::dimension>::Handle>(h, [](auto* p) { amd::Api<Scalar, Node::dimension>::destroy(p); });
         pull();
@@ -784,6 +795,39 @@ DeviceArray<PrecomputedTri<typename Node::Scalar>> permuted_triangles(const Bvh<
     check(Api<T, 3>::precompute(d_tris.data(), Api<T, 3>::device_prim_ids(bvh.device()), tris.size(), out.data()), "precompute_tris");
     check(bvh_amd_synchronize(nullptr), "synchronize");
     return out;
+}
+
+// Bvh::refit(leaf_fn) (reference bvh.h:211-218) with the usual leaf_fn — box = empty, extend over bboxes[prim_ids[i]] — run on the device
+// from primitives in HBM (include/bvh_amd.h: bvhXX_refit_boxes / bvh3X_refit_tris). `bboxes` / `tris` are in ORIGINAL order.
+// The mirror's public `nodes` must not be left stale, so these push pending edits of `nodes`, run the device refit and pull the
+// result back: two copies of the node array per call, and — because the push rebuilds the device twin from `nodes` — the measured
+// launch plan and the tree depth do NOT survive a call made through these functions. A frame loop that wants no copies and wants to
+// keep the plan calls the C entry points on bvh.device() directly (bvh3f_refit_tris(bvh.device(), ...)) and reads `nodes` only when
+// it needs them (Bvh::sync_from_device()).
+template <typename Node>
+void refit_boxes(Bvh<Node>& bvh, const DeviceArray<BBox<typename Node::Scalar, Node::dimension>>& bboxes) {
+    using T = typename Node::Scalar;
+    bvh.sync_to_device();
+    check(Api<T, Node::dimension>::refit_boxes(bvh.device(), bboxes.data(), bboxes.size()), "refit_boxes");
+    bvh.sync_from_device();
+}
+// ... from triangles; `out` (resized if it has another size) receives the BVH-order PrecomputedTri array the traversal takes
+template <typename Node>
+void refit_tris(Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, DeviceArray<PrecomputedTri<typename Node::Scalar>>& out) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "triangles are 3D (tri.h)");
+    bvh.sync_to_device();
+    if (out.size() != bvh.prim_ids.size()) out = DeviceArray<PrecomputedTri<T>>(bvh.prim_ids.size());
+    check(Api<T, 3>::refit_tris(bvh.device(), tris.data(), tris.size(), out.data()), "refit_tris");
+    bvh.sync_from_device();
+}
+// the traversal records a random line through the scene is expected to fetch (bvh3X_traversal_cost): refit again, or rebuild?
+template <typename Node>
+double traversal_cost(const Bvh<Node>& bvh) {
+    static_assert(Node::dimension == 3, "traversal_cost: 3D trees only");
+    double cost = 0.0;
+    check(Api<typename Node::Scalar, 3>::traversal_cost(bvh.device(), &cost), "traversal_cost");
+    return cost;
 }
 
 // Bvh::intersect<IsAnyHit, IsRobust> (reference bvh.h:160-182) for a batch of rays with the closest/any-hit triangle

@@ -330,6 +330,55 @@ BVH_AMD_API void bvh3d_refit(struct bvh3d*);
  * bvhXX_optimize_config (NULL config = the reference's defaults) and bvhXX_refit_status: 0 or a negative code + bvh_amd_last_error(). */
 BVH_AMD_API int bvh3f_refit_status(struct bvh3f*);
 BVH_AMD_API int bvh3d_refit_status(struct bvh3d*);
+
+/* ---- refit from moved primitives, entirely on the device (additive) ------------------------------------------------------
+ * The resident form of the reference's Bvh::refit(leaf_fn) (bvh.h:211-218): moved primitives in HBM in, a tree ready to trace out,
+ * on the caller's stream, no host copy. For EVERY leaf of the node array (reachable or not, like traverse_bottom_up)
+ *     box = BBox::make_empty()                                            (+max, -max; bbox.h:40-44)
+ *     for i in [first_id, first_id + prim_count): box.extend(bboxes[prim_ids[i]])      in this order (bbox.h:23-27)
+ * with extend = robust_min / robust_max (utils.h:41-43: `a < b ? a : b` / `a > b ? a : b` with the accumulated value as a). Order and
+ * the direction of the comparison are part of the contract: whenever `a < b` is false the OTHER value is taken, so of +0 and -0 the
+ * one met last stays, and a NaN component replaces the accumulated value and is itself replaced by the next primitive's (a NaN in
+ * the leaf's last primitive stays in the box) — exactly what the loop a user of the reference writes inside refit(leaf_fn) does. Every inner box is then left.extend(right), children before parents. 2D trees keep z = (+0, +0).
+ *
+ * refit_boxes: d_bboxes has the layout of the build input (bvhXX_build_device: n x {min, max}; 2D: n x {min.x, min.y, max.x, max.y})
+ *   and is indexed by ORIGINAL primitive id, i.e. by the values of prim_ids.
+ * refit_tris (3D): d_tris9 = n x {p0, p1, p2} in original order; bboxes[j] = Tri::get_bbox() = BBox(p0).extend(p1).extend(p2)
+ *   (tri.h:24, bit-identical to bvh_amd_tri_bounds3X). If d_tris12_out is not NULL it receives PrecomputedTri(tris[prim_ids[i]]) for
+ *   every BVH-order slot i, byte-identical to bvh_amd_precompute_tris3X(d_tris9, bvhXX_device_prim_ids(bvh), prim_count, out): one
+ *   call per frame takes deformed vertices to a traceable (tree, primitives) pair. It may be the array earlier launches read: the
+ *   call is ordered on `stream` like any other work.
+ *
+ * Both calls
+ *   - are asynchronous on `stream` (NULL = the default stream) from the second call on a tree: no synchronisation, no copy of node
+ *     arrays, no allocation (scratch comes from the per-stream block cache). The first call pays one read-back (the largest prim id);
+ *   - update in place both device representations: the reference-layout nodes (serialize_device, extract, optimize, broadcast keep
+ *     working) and the traversal records (same allocation). Index words are never written;
+ *   - keep what depends on the topology only: the tree depth, the measured launch plan (a plan affects speed, never results), the
+ *     device prim ids. The root box the ray / query reordering scales its keys by is refreshed behind an event the next launch waits
+ *     for; the expected-visits figure of the plan predictor is left as it was (bvh3X_traversal_cost recomputes it);
+ *   - mark the host mirror stale instead of copying it back; the next accessor refills it. Node pointers obtained from
+ *     bvhXX_get_node BEFORE the call still point at valid memory (they are invalidated by append only), but what is written through
+ *     them after the call and before the next accessor is discarded by that refill: fetch node pointers again after a refit_* call.
+ *     If the mirror is valid when the call arrives (an accessor ran since the last device operation, or the tree came from
+ *     from_nodes / load / deserialize), it is pushed, validated and the records are rebuilt first, exactly as bvhXX_refit does on
+ *     every call — leaf boxes and inner boxes set through the mirror do not survive the refit, index edits do. A one-off, not a
+ *     per-frame cost, as long as the frame loop does not touch the mirror;
+ *   - validate before touching anything: bvh and pointers non-NULL, n_boxes / n_tris larger than the largest value in prim_ids.
+ *     On failure: a negative code, bvh_amd_last_error(), tree unchanged;
+ *   - are NOT re-entrant (they write the tree): launches that read the tree (bvhXX_intersect_rays_*, bvhXX_closest_points_*,
+ *     serialize_device, ...) must be ordered before / after the refit by the caller (same stream, or events). */
+BVH_AMD_API int bvh3f_refit_boxes(struct bvh3f*, const float* d_bboxes, size_t n_boxes, void* stream);
+BVH_AMD_API int bvh3d_refit_boxes(struct bvh3d*, const double* d_bboxes, size_t n_boxes, void* stream);
+BVH_AMD_API int bvh3f_refit_tris(struct bvh3f*, const float* d_tris9, size_t n_tris, float* d_tris12_out, void* stream);
+BVH_AMD_API int bvh3d_refit_tris(struct bvh3d*, const double* d_tris9, size_t n_tris, double* d_tris12_out, void* stream);
+/* The figure to watch to decide "refit again or rebuild" (it grows as a refitted tree degrades): the number of traversal records a
+ * random line through the scene is expected to fetch = the sum over the inner nodes OTHER THAN THE ROOT (the terms are taken per
+ * inner child of a record, and the root is nobody's child) of half_area(node) / half_area(root), half_area = xy + yz + zx, computed
+ * from the CURRENT records, each term truncated to units of 2^-16 (an integer sum: the result does not depend on the order of the
+ * atomics). Synchronous on `stream` (one read-back). 3D trees only. */
+BVH_AMD_API int bvh3f_traversal_cost(struct bvh3f*, double* cost_out, void* stream);
+BVH_AMD_API int bvh3d_traversal_cost(struct bvh3d*, double* cost_out, void* stream);
 BVH_AMD_API int bvh3f_sync_device(struct bvh3f*);
 BVH_AMD_API int bvh3d_sync_device(struct bvh3d*);
 BVH_AMD_API void bvh3f_append_node(struct bvh3f*);
@@ -421,7 +470,8 @@ BVH_AMD_API int bvh_amd_shade_eyelight3d(const double* d_tris12, const struct bv
 /* ---- batched traversal: Bvh::intersect<IsAnyHit, IsRobust> (bvh.h:160-182) for n rays ---------- */
 /* d_prims are in BVH order (prims[i] belongs to prim_ids[i]), like the reference's permuted
  * primitives (test/simple_example.cpp:57-65). d_counters may be NULL. Re-entrant like Bvh::intersect on a const Bvh: launches
- * of one BVH may be issued concurrently from several host threads and on several streams (up to 64 in flight per BVH). */
+ * of one BVH may be issued concurrently from several host threads and on several streams (up to 64 in flight per BVH).
+ * (bvhXX_refit_boxes / bvh3X_refit_tris WRITE the tree and are not re-entrant: order them against these launches.) */
 BVH_AMD_API int bvh3f_intersect_rays_tri(const struct bvh3f*, const float* d_tris12, const struct bvh_ray3f* d_rays,
     size_t n, unsigned flags, struct bvh_hit3f* d_hits, struct bvh_amd_counters* d_counters, void* stream);
 BVH_AMD_API int bvh3d_intersect_rays_tri(const struct bvh3d*, const double* d_tris12, const struct bvh_ray3d* d_rays,
@@ -574,6 +624,7 @@ BVH_AMD_API void bvh2f_optimize(struct bvh_thread_pool*, struct bvh2f*);
 BVH_AMD_API int bvh2f_optimize_config(struct bvh2f*, const struct bvh_amd_optimize_config*);
 BVH_AMD_API void bvh2f_refit(struct bvh2f*);
 BVH_AMD_API int bvh2f_refit_status(struct bvh2f*);
+BVH_AMD_API int bvh2f_refit_boxes(struct bvh2f*, const float* d_bboxes4, size_t n_boxes, void* stream);     /* see bvh3f_refit_boxes */
 BVH_AMD_API int bvh2f_sync_device(struct bvh2f*);
 BVH_AMD_API void bvh2f_append_node(struct bvh2f*);
 BVH_AMD_API void bvh2f_remove_last_node(struct bvh2f*);
@@ -620,6 +671,7 @@ BVH_AMD_API void bvh2d_optimize(struct bvh_thread_pool*, struct bvh2d*);
 BVH_AMD_API int bvh2d_optimize_config(struct bvh2d*, const struct bvh_amd_optimize_config*);
 BVH_AMD_API void bvh2d_refit(struct bvh2d*);
 BVH_AMD_API int bvh2d_refit_status(struct bvh2d*);
+BVH_AMD_API int bvh2d_refit_boxes(struct bvh2d*, const double* d_bboxes4, size_t n_boxes, void* stream);
 BVH_AMD_API int bvh2d_sync_device(struct bvh2d*);
 BVH_AMD_API void bvh2d_append_node(struct bvh2d*);
 BVH_AMD_API void bvh2d_remove_last_node(struct bvh2d*);
