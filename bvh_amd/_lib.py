@@ -98,6 +98,7 @@ _SIGS = {
     "bvh_amd_std_sort_ids3f": (_I, [_P, _Z, _P, _P]),
     "bvh_amd_std_sort_ids3d": (_I, [_P, _Z, _P, _P]),
     "bvh_amd_radix_sort_pairs_u32": (_I, [_P, _P, _Z, _I, _P]),
+    "bvh_amd_offsets_from_counts": (_I, [_P, _Z, _P, _P]),
 }
 _SIGS_T = {
     "bvh{S}_build": (_P, [_P, _P, _P, _Z, _P]),
@@ -148,6 +149,8 @@ _SIGS_T = {
     "bvh{S}_prepare_trace": (_I, [_P, _Z, _P]),
     "bvh{S}_closest_points_tri": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P]),
     "bvh{S}_closest_points_sphere": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P]),
+    "bvh{S}_radius_search_tri": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P, _P, _P, _P]),
+    "bvh{S}_radius_search_sphere": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P, _P, _P, _P]),
     # one ray, host leaf callback (c_api/bvh.h:277-295): (bvh, ray, callback struct)
     "bvh{S}_intersect_ray": (None, [_P, _P, _P]),
     "bvh{S}_intersect_ray_any": (None, [_P, _P, _P]),
@@ -183,6 +186,7 @@ def ray_visitor_types(suffix: str):
 _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_intersect_rays_tri", "bvh{S}_prepare_trace",     # tri.h is 3D only,
             "bvh{S}_build_minitree_device",                                                           # and so is the mini-tree grid
             "bvh{S}_closest_points_tri", "bvh{S}_closest_points_sphere",                              # and the closest-point queries
+            "bvh{S}_radius_search_tri", "bvh{S}_radius_search_sphere",                                # and the radius queries
             "bvh{S}_refit_tris", "bvh{S}_traversal_cost")                                             # (tri.h; the 3D area term)
 
 

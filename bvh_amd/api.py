@@ -552,6 +552,104 @@ def closest_points(bvh: Bvh, prims, points, max_distance: float = float("inf"), 
     return out
 
 
+def _radius_args(bvh: Bvh, prims, points, radius, leaf: str, who: str):
+    """The checks and the (n, 4) query tensor closest_points makes, for the radius queries: (queries, prims, scalar dtype)."""
+    torch = _torch()
+    if bvh.dim != 3:
+        raise TypeError(f"{who}: 3D trees only")
+    if leaf not in ("tri", "sphere"):
+        raise ValueError("leaf is 'tri' or 'sphere'")
+    dt = torch.float32 if bvh._s[1] == "f" else torch.float64
+    pts = _dev(points)
+    if pts.dim() != 2 or pts.shape[1] not in (3, 4):
+        raise ValueError("points must be (n, 3) or (n, 4)")
+    if pts.dtype != dt:
+        raise TypeError("points dtype must match the BVH scalar type")
+    if pts.shape[1] == 3:
+        if radius is None:
+            raise ValueError("(n, 3) points need a radius")
+        q = torch.empty((pts.shape[0], 4), dtype=dt, device=pts.device)
+        q[:, :3] = pts
+        q[:, 3] = float(radius)
+    else:
+        if radius is not None:
+            raise ValueError("(n, 4) points carry their own radius: leave radius at its default")
+        q = pts
+    p = _dev(prims)
+    if p.dtype != dt:
+        raise TypeError("prims dtype must match the BVH scalar type")
+    return q, p, dt
+
+
+def _sort_flags(sort_queries, original_ids=False):
+    return (0 if sort_queries is None else RayFlags.SORTED if sort_queries else RayFlags.UNSORTED) | (8 if original_ids else 0)
+
+
+def offsets_from_counts(counts):
+    """(n + 1,) int64 offsets {0, c0, c0 + c1, ...} of an (n,) int32 tensor of counts, on the device and without a read-back
+    (bvh_amd_offsets_from_counts)."""
+    torch = _torch()
+    c = _dev(counts)
+    if c.dtype != torch.int32 or c.dim() != 1:
+        raise TypeError("counts must be a 1-D int32 tensor")
+    out = torch.empty(c.shape[0] + 1, dtype=torch.int64, device=c.device)
+    _lib.check(_lib.load().bvh_amd_offsets_from_counts(c.data_ptr() if c.shape[0] else None, c.shape[0], out.data_ptr(), _stream()), "offsets_from_counts")
+    return out
+
+
+def radius_count(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", sort_queries=None, counters: bool = False):
+    """For each point, how many primitives lie within the radius (bvhXX_radius_search_* without lists): an int32 (n,) tensor; with
+    counters also (pairs, tests, leaves). points: (n, 3) with the scalar radius, or (n, 4) with a per-query radius in column 3."""
+    torch = _torch()
+    q, p, _ = _radius_args(bvh, prims, points, radius, leaf, "radius_count")
+    n = q.shape[0]
+    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_radius_search_{leaf}")
+    _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, int(_sort_flags(sort_queries)), counts.data_ptr(), None, None, None,
+                  cnt.data_ptr() if counters else None, _stream()), "radius_count")
+    return (counts, cnt) if counters else counts
+
+
+def radius_search(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", max_per_query=None, distances: bool = True,
+                  original_ids: bool = False, sort_queries=None, counters: bool = False):
+    """For each point, the primitives within the radius (bvhXX_radius_search_*), in the order the tree fixes (depth-first, left child
+    first, ascending index inside a leaf). prims are in BVH order, as for closest_points; points: (n, 3) with the scalar radius, or
+    (n, 4) with a per-query radius in column 3. Returns (offsets, ids, dist): offsets int64 (n + 1,), query q owns
+    ids[offsets[q]:offsets[q + 1]] (int32 BVH-order indices, or bvh.prim_ids[i] with original_ids) and the distances beside them
+    (None without `distances`).
+      max_per_query=None: exact lists — a count pass, the offsets on the device, one read of offsets[-1] to size the lists, a fill pass.
+      max_per_query=k: one pass, k slots per query (offsets = k * arange(n + 1)): the first k of each list, the unused slots holding
+        -1 (INVALID) and the query's radius; returns (offsets, ids, dist, counts), counts (int32, untruncated) telling which lists
+        overflowed.
+    With counters, (pairs, tests, leaves) of the pass that wrote the lists is appended to the result."""
+    torch = _torch()
+    q, p, dt = _radius_args(bvh, prims, points, radius, leaf, "radius_search")
+    n = q.shape[0]
+    dev = q.device
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_radius_search_{leaf}")
+    flags = int(_sort_flags(sort_queries, original_ids))
+    cnt = torch.zeros(3, dtype=torch.int64, device=dev) if counters else None
+    counts = torch.zeros(n, dtype=torch.int32, device=dev)
+    if max_per_query is None:
+        _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, flags, counts.data_ptr(), None, None, None, None, _stream()), "radius_search")
+        offsets = offsets_from_counts(counts)
+        total = int(offsets[-1].item())
+    else:
+        k = int(max_per_query)
+        if k < 0:
+            raise ValueError("max_per_query must not be negative")
+        offsets = torch.arange(n + 1, dtype=torch.int64, device=dev) * k
+        total = n * k
+    ids = torch.empty(max(total, 1), dtype=torch.int32, device=dev)               # (never a null pointer: an empty result is still a list)
+    dist = torch.empty(max(total, 1), dtype=dt, device=dev) if distances else None
+    _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, flags, counts.data_ptr() if max_per_query is not None else None, offsets.data_ptr(), ids.data_ptr(),
+                  dist.data_ptr() if distances else None, cnt.data_ptr() if counters else None, _stream()), "radius_search")
+    ids, dist = ids[:total], dist[:total] if distances else None
+    out = (offsets, ids, dist) if max_per_query is None else (offsets, ids, dist, counts)
+    return out + (cnt,) if counters else out
+
+
 def hits_to_numpy(hits) -> np.ndarray:
     a = hits.detach().cpu().numpy()
     return a.view(HITF if a.dtype == np.float32 else HITD).reshape(-1)

@@ -535,6 +535,19 @@ int closest(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, cons
     return launch_closest<T>(b, leaf, d_prims, d_queries4, n, flags, d_hits, d_counters, static_cast<hipStream_t>(stream));
 }
 
+template <typename T>
+int radius_search(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned flags, uint32_t* d_counts,
+                  const uint64_t* d_offsets, uint32_t* d_list_prims, T* d_list_dist, bvh_amd_counters* d_counters, void* stream)
+{
+    if (!bvh) return fail(BVH_AMD_ERR_ARG, "radius_search: null bvh");
+    const BvhImpl<T>& b = *impl<T>(bvh);
+    int cur = -1;
+    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
+    if (n != 0 && cur != b.device) return fail(BVH_AMD_ERR_ARG, "radius_search: BVH lives on another device than the current one");
+    return launch_radius<T>(b, leaf, d_prims, d_queries4, n, flags, d_counts, d_offsets, d_list_prims, d_list_dist, d_counters,
+                            static_cast<hipStream_t>(stream));
+}
+
 // bvhXX_intersect_ray{,_any}{,_robust} (c_api/bvh.h:277-295 over bvh_impl.h:235-250): one ray, the leaves go to the caller's
 // function. The walk runs on the device (traverse.hip, ray_step_kernel); `ray` is the family's own struct.
 template <typename T, int D>
@@ -757,6 +770,12 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_closest_points_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned flags,    \
                                        bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                          \
         return closest<T>(b, LEAF_SPHERE, prims, queries, n, flags, hits, cnt, s); }                                \
+    int bvh##S##_radius_search_tri(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned flags, uint32_t* counts, \
+                                   const uint64_t* offsets, uint32_t* list_prims, T* list_dist, bvh_amd_counters* cnt, void* s) { \
+        return radius_search<T>(b, LEAF_TRIANGLE, prims, queries, n, flags, counts, offsets, list_prims, list_dist, cnt, s); } \
+    int bvh##S##_radius_search_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned flags, uint32_t* counts, \
+                                      const uint64_t* offsets, uint32_t* list_prims, T* list_dist, bvh_amd_counters* cnt, void* s) { \
+        return radius_search<T>(b, LEAF_SPHERE, prims, queries, n, flags, counts, offsets, list_prims, list_dist, cnt, s); } \
     int bvh##S##_prepare_trace(const bvh##S* b, size_t n_rays_hint, void* s) {                                      \
         if (!b) return fail(BVH_AMD_ERR_ARG, "prepare_trace: null bvh");                                            \
         int cur = -1;                                                                                               \
@@ -866,6 +885,9 @@ BVH_AMD_IMPL2(double, 2d)
 BVH_AMD_IMPL_RAY(float, 2f, bvh_intersect_callbackf, bvh_amd_ray_visitorf, 2, impl2)
 BVH_AMD_IMPL_RAY(double, 2d, bvh_intersect_callbackd, bvh_amd_ray_visitord, 2, impl2)
 
+int bvh_amd_offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets, void* stream) {
+    return offsets_from_counts(d_counts, n, d_offsets, static_cast<hipStream_t>(stream));
+}
 int bvh_amd_std_sort_ids3f(const float* d_keys, size_t n, uint32_t* d_ids_out, void* stream) {
     return std_sort_ids<float>(d_ids_out, d_keys, static_cast<uint32_t>(n), 1, 0, 1, static_cast<hipStream_t>(stream));
 }

@@ -9,13 +9,14 @@
 //     box distance^2 so that a popped entry is re-checked against the best distance before anything is fetched;
 //   * the stack: kClosestLds entries in LDS, the rest of 64 in per-lane scratch, beyond 64 (deep trees) in HBM;
 //   * optionally the batch is read in the order of the Hilbert cell of each point in the root box (ray_key.h, radix sort): neighbouring
-//     lanes then walk the same records. Records are always written in the caller's order.
+//     lanes then walk the same records (query_order.h). Records are always written in the caller's order.
 //
 // Compiled with -ffp-contract=off; division and sqrt are the correctly rounded forms (bit-identical to the host harness).
 
 #include "common.h"
 #include "trace_device.h"
 #include "ray_key.h"
+#include "query_order.h"
 #include "closest_body.inc"
 
 #include <algorithm>
@@ -46,32 +47,6 @@ __global__ void __launch_bounds__(kBlock) closest_kernel(ClosestArgs<T> a) {
             atomicAdd(&a.counters->leaves, cnt[2]);
         }
     }
-}
-
-// Sort keys of the queries: ray_key of the ray {p, dir = +0, 0, max_distance} without chord classes (the octant bits are 0), one
-// radix tile per block with its first-digit histogram, like traverse.hip's ray_keys_kernel.
-template <typename T>
-__global__ void __launch_bounds__(1024) closest_keys_kernel(const T* queries, uint32_t n, T lx, T ly, T lz, T sx, T sy, T sz, uint32_t cells,
-                                                            uint32_t* keys, uint32_t* hist, uint32_t tiles) {
-    __shared__ uint32_t h[256];
-    if (threadIdx.x < 256) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * uint32_t(kRadixTileU32);
-#pragma unroll
-    for (int s0 = 0; s0 < kRadixTileU32 / 1024; ++s0) {
-        const uint32_t i = base + uint32_t(s0) * 1024u + threadIdx.x;
-        if (i < n) {
-            T q[4];
-            load_prim4(queries + 4ull * i, q);
-            const T r[8] = { q[0], q[1], q[2], T(0), T(0), T(0), T(0), q[3] };
-            const int hilbert_bits = 31 - __clz(cells);
-            const uint32_t key = ray_key<T>(r, lx, ly, lz, sx, sy, sz, cells, hilbert_bits, 0, T(0));
-            keys[i] = key;
-            atomicAdd(&h[key & 0xFFu], 1u);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 256) hist[size_t{threadIdx.x} * tiles + blockIdx.x] = h[threadIdx.x];
 }
 
 // Reordering a batch costs a key pass and three radix passes (~0.03 ns per query) and pays once the batch is large enough for
@@ -153,29 +128,9 @@ int launch_closest(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T
     static const size_t sort_min = static_cast<size_t>(std::max(0, BVH_DEV_INT("BVH_AMD_CLOSEST_SORT_MIN", static_cast<int>(kClosestSortMin))));   // developer knob
     const bool reorder = n < (size_t{1} << 31) && ((flags & BVH_AMD_RAY_SORTED) ? n > 1 : (flags & BVH_AMD_RAY_UNSORTED) ? false : n >= sort_min);
     if (reorder) {
-        const uint32_t n32 = static_cast<uint32_t>(n);
-        const size_t words = 4 * n + radix_sort_hist_words(n32, 1);               // keys + tmp, indices + tmp, histogram
-        const hipError_t e = scratch_alloc(&sort_mem, words * sizeof(uint32_t), &sort_tag);
-        if (e != hipSuccess) { sort_mem = nullptr; return release(fail(BVH_AMD_ERR_HIP, std::string("closest_points: no scratch for the query sort: ") + hipGetErrorString(e))); }
-        uint32_t *keys = static_cast<uint32_t*>(sort_mem), *vals = keys + n, *kt = vals + n, *vt = kt + n, *hist = vt + n;
         static const int cell_bits = std::max(1, std::min(8, BVH_DEV_INT("BVH_AMD_CLOSEST_KEY_BITS", 7)));       // developer knob
-        const uint32_t cells = 1u << cell_bits;
-        T lo[3], sc[3];
-        if (const int rc0 = b.wait_refit()) return release(rc0);      // root_bounds follows a refit_* that changed the boxes on the device
-        for (int k = 0; k < 3; ++k) {
-            const T ext = b.root_bounds[2 * k + 1] - b.root_bounds[2 * k];
-            lo[k] = b.root_bounds[2 * k];
-            sc[k] = ext > T(0) ? T(cells) / ext : T(0);
-        }
-        const uint32_t tiles = (n32 + kRadixTileU32 - 1) / kRadixTileU32;
-        hipLaunchKernelGGL(closest_keys_kernel<T>, dim3(tiles), dim3(1024), 0, stream, d_queries, n32, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], cells,
-                           keys, hist, tiles);
-        BVH_HIP_TRY(hipGetLastError(), BVH_AMD_ERR_HIP);
-        uint32_t* order = nullptr;
-        const int rc = radix_sort_pairs<uint32_t>(keys, vals, kt, vt, n32, 1, 3 * cell_bits + 3, stream, hist, /*iota_vals=*/true, /*keys_wanted=*/false, &order,
-                                                  /*first_hist_done=*/true);
+        const int rc = query_order<T>(b, d_queries, n, cell_bits, "closest_points", stream, &sort_mem, &sort_tag, &a.order);
         if (rc) return release(rc);
-        a.order = order;
     }
 
     const bool stats = d_counters != nullptr, deep = a.deep_cap != 0;

@@ -318,6 +318,8 @@ template <> struct Api<float, 3> {
     static int trace_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3f_intersect_rays_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int closest_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3f_closest_points_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3f_closest_points_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
+    static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
+    static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, float*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitorf v{ user, leaf, inner };
         return bvh3f_intersect_ray_visit(h, static_cast<const bvh_ray3f*>(ray), start, f, &v);
@@ -352,6 +354,8 @@ template <> struct Api<double, 3> {
     static int trace_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3d_intersect_rays_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int closest_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3d_closest_points_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3d_closest_points_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
+    static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
+    static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, double*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitord v{ user, leaf, inner };
         return bvh3d_intersect_ray_visit(h, static_cast<const bvh_ray3d*>(ray), start, f, &v);
@@ -891,6 +895,79 @@ void closest_points_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typenam
     DeviceArray<Hit<T>> d_hits(queries.size());
     closest_points_batch(bvh, spheres, d_queries, d_hits);
     d_hits.download(hits);
+}
+
+// For each query, every primitive within its max_distance (include/bvh_amd.h: bvhXX_radius_search_*), in the order the tree fixes.
+// Device form: any of the outputs may be null, as in the C ABI — `counts` (queries.size() entries: untruncated list lengths),
+// `offsets` (queries.size() + 1 entries; null = count pass) with `list_prims` (BVH-order indices, invalid in the unused rest of a
+// segment) and optionally `list_dist` (distances, max_distance in the unused rest).
+namespace detail {
+template <typename T>
+using RadiusFn = int (*)(const typename Api<T, 3>::Handle*, const void*, const void*, size_t, unsigned, uint32_t*, const uint64_t*, uint32_t*, void*);
+template <typename T>
+void radius_device(RadiusFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, const DeviceArray<PointQuery<T>>& queries, DeviceArray<uint32_t>* counts,
+                   const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims, DeviceArray<T>* list_dist, const char* what) {
+    const size_t n = queries.size();
+    if ((counts && counts->size() < n) || (offsets && offsets->size() < n + 1)) throw Error(std::string(what) + ": counts need n entries, offsets n + 1");
+    if (list_prims && list_dist && list_dist->size() < list_prims->size()) throw Error(std::string(what) + ": distances need an entry per listed primitive");
+    check(fn(h, prims, queries.data(), n, 0u, counts ? counts->data() : nullptr, offsets ? offsets->data() : nullptr, list_prims ? list_prims->data() : nullptr,
+             list_dist ? list_dist->data() : nullptr), what);
+}
+// count, offsets on the device, one read of offsets[n] to size the lists, fill
+template <typename T>
+void radius_host(RadiusFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, std::span<const PointQuery<T>> queries, std::vector<uint64_t>& offsets,
+                 std::vector<uint32_t>& list_prims, std::vector<T>* list_dist, const char* what) {
+    const size_t n = queries.size();
+    offsets.assign(n + 1, 0);
+    list_prims.clear();
+    if (list_dist) list_dist->clear();
+    if (n == 0) return;
+    DeviceArray<PointQuery<T>> d_queries(queries);
+    DeviceArray<uint32_t> d_counts(n);
+    DeviceArray<uint64_t> d_offsets(n + 1);
+    radius_device<T>(fn, h, prims, d_queries, &d_counts, nullptr, nullptr, nullptr, what);
+    check(bvh_amd_offsets_from_counts(d_counts.data(), n, d_offsets.data(), nullptr), "offsets_from_counts");
+    d_offsets.download(std::span<uint64_t>(offsets));
+    const size_t total = static_cast<size_t>(offsets[n]);
+    list_prims.resize(total);
+    if (list_dist) list_dist->resize(total);
+    if (total == 0) return;
+    DeviceArray<uint32_t> d_list(total);
+    DeviceArray<T> d_dist(list_dist ? total : 0);
+    radius_device<T>(fn, h, prims, d_queries, nullptr, &d_offsets, &d_list, list_dist ? &d_dist : nullptr, what);
+    d_list.download(std::span<uint32_t>(list_prims));
+    if (list_dist) d_dist.download(std::span<T>(*list_dist));
+}
+} // namespace detail
+
+template <typename Node>
+void radius_search_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims,
+                         const DeviceArray<PointQuery<typename Node::Scalar>>& queries, DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets,
+                         DeviceArray<uint32_t>* list_prims, DeviceArray<typename Node::Scalar>* list_dist = nullptr) {
+    using T = typename Node::Scalar;
+    detail::radius_device<T>(&Api<T, 3>::radius_tri, bvh.device(), prims.data(), queries, counts, offsets, list_prims, list_dist, "radius_search_tri");
+}
+template <typename Node>
+void radius_search_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres,
+                         const DeviceArray<PointQuery<typename Node::Scalar>>& queries, DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets,
+                         DeviceArray<uint32_t>* list_prims, DeviceArray<typename Node::Scalar>* list_dist = nullptr) {
+    using T = typename Node::Scalar;
+    detail::radius_device<T>(&Api<T, 3>::radius_sphere, bvh.device(), spheres.data(), queries, counts, offsets, list_prims, list_dist, "radius_search_sphere");
+}
+// Host form: exact lists. Query q's primitives are list_prims[offsets[q] .. offsets[q + 1]) (and their distances in *list_dist).
+template <typename Node>
+void radius_search_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims,
+                         std::span<const PointQuery<typename Node::Scalar>> queries, std::vector<uint64_t>& offsets, std::vector<uint32_t>& list_prims,
+                         std::vector<typename Node::Scalar>* list_dist = nullptr) {
+    using T = typename Node::Scalar;
+    detail::radius_host<T>(&Api<T, 3>::radius_tri, bvh.device(), prims.data(), queries, offsets, list_prims, list_dist, "radius_search_tri");
+}
+template <typename Node>
+void radius_search_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres,
+                         std::span<const PointQuery<typename Node::Scalar>> queries, std::vector<uint64_t>& offsets, std::vector<uint32_t>& list_prims,
+                         std::vector<typename Node::Scalar>* list_dist = nullptr) {
+    using T = typename Node::Scalar;
+    detail::radius_host<T>(&Api<T, 3>::radius_sphere, bvh.device(), spheres.data(), queries, offsets, list_prims, list_dist, "radius_search_sphere");
 }
 
 // ---- multi-GPU: rays shard, the scene is broadcast once over RCCL inside the library -------------------------------

@@ -117,7 +117,7 @@ enum bvh_amd_ray_flags {
                                   whose node records exceed the 32 MB of L2 and through which a random line is expected to fetch
                                   >= 100 records (sum of area(node) / area(root) over the inner nodes): +40..50 % there      */
     BVH_AMD_RAY_UNSORTED = 16u, /* never reorder (rays already coherent, or no scratch memory to spare: 16 bytes per ray)  */
-                                /* (SORTED / UNSORTED / ORIGINAL_IDS apply to bvhXX_closest_points_* queries too) */
+                                /* (SORTED / UNSORTED / ORIGINAL_IDS apply to bvhXX_closest_points_* and bvhXX_radius_search_* queries too) */
     BVH_AMD_RAY_ORIGINAL_IDS = 8u  /* hit.prim = the ORIGINAL primitive id bvh.prim_ids[i] (what c_api_example.c:265-268 looks up per
                                       hit) instead of the BVH-order index i: one more pass over the hit records, on the device    */
 };
@@ -502,6 +502,43 @@ BVH_AMD_API int bvh3f_closest_points_sphere(const struct bvh3f*, const float* d_
     struct bvh_hit3f* d_out, struct bvh_amd_counters* d_counters, void* stream);
 BVH_AMD_API int bvh3d_closest_points_sphere(const struct bvh3d*, const double* d_sph4, const double* d_queries4, size_t n, unsigned flags,
     struct bvh_hit3d* d_out, struct bvh_amd_counters* d_counters, void* stream);
+
+/* ---- batched radius queries: for each point, every primitive within a distance -------------------------------------------------- */
+/* Queries and primitives as for bvhXX_closest_points_* (n x {x, y, z, max_distance}; BVH-order PrecomputedTri or Sphere<T, 3>). With
+ * r2 = max_distance * max_distance, the result of a query is the LIST of BVH-order indices i with d2(i) <= r2, d2 being the squared
+ * distance bvhXX_closest_points_* measures (solid triangle; max(|q - c| - r, 0)^2 for a sphere). A subtree is entered iff the
+ * squared distance of its box to the point is <= r2.
+ *   order:   fixed by the tree. The walk is depth-first, a node's left child (first_id) before its right (first_id + 1), ascending
+ *            index inside a leaf; there is no near-first ordering.
+ *   invalid: a NaN coordinate and a negative or NaN max_distance give an empty list; +inf gives every reachable primitive; 0 gives the
+ *            primitives at distance exactly 0.
+ *   output:  d_counts[q] (n entries, or NULL) = the number of primitives within the radius, NEVER truncated. d_offsets (n + 1 entries,
+ *            or NULL = count pass, no list written): query q owns [d_offsets[q], d_offsets[q + 1]) of d_list_prims (required iff
+ *            d_offsets) and d_list_dist (optional, sqrt(d2) correctly rounded, parallel to d_list_prims). The first min(count, segment
+ *            length) entries of its list are written there in walk order; the rest of the segment is padded with BVH_AMD_INVALID and
+ *            distance = the query's max_distance (the miss record of closest_points). Nothing outside a query's segment is written;
+ *            a segment whose end does not exceed its begin is empty. At least one of d_counts and d_offsets must be given. Hence:
+ *            count, bvh_amd_offsets_from_counts, fill = exact compressed-sparse-row lists; d_offsets = k * {0, 1, ..., n} = k slots
+ *            per query in one pass, d_counts telling which lists overflowed; d_counts alone = count only.
+ *   flags:   BVH_AMD_RAY_ORIGINAL_IDS lists bvh.prim_ids[i] instead of i (the order stays the walk's); BVH_AMD_RAY_SORTED /
+ *            BVH_AMD_RAY_UNSORTED as for closest_points (with neither, batches of >= 1M queries are reordered internally). Any other
+ *            bit: BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * A query's count and list depend only on the tree, the primitives and the query: not on batch size, position or order, the
+ * reordering flags, the stream or the thread. d_counters (optional) receives {pair records fetched, primitives tested, leaves
+ * visited}. Alignment: d_prims and d_queries4 16 bytes, d_offsets and d_counters 8, d_counts, d_list_prims and a float d_list_dist 4,
+ * a double d_list_dist 8. 3D trees only; a 2D tree, a NULL or misaligned pointer and a tree without a device copy are refused with
+ * BVH_AMD_ERR_ARG. Re-entrant on a const tree (no work slot of the tree is claimed). */
+BVH_AMD_API int bvh3f_radius_search_tri(const struct bvh3f*, const float* d_tris12, const float* d_queries4, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, float* d_list_dist, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_radius_search_tri(const struct bvh3d*, const double* d_tris12, const double* d_queries4, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, double* d_list_dist, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_radius_search_sphere(const struct bvh3f*, const float* d_sph4, const float* d_queries4, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, float* d_list_dist, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_radius_search_sphere(const struct bvh3d*, const double* d_sph4, const double* d_queries4, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, double* d_list_dist, struct bvh_amd_counters* d_counters, void* stream);
+/* d_offsets[0..n] = {0, c0, c0 + c1, ...} of d_counts[0..n): 64-bit sums, asynchronous on `stream` (no host read-back). n == 0
+ * writes d_offsets[0] = 0. */
+BVH_AMD_API int bvh_amd_offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets, void* stream);
 
 /* Optional, additive: pays NOW what the first large batch through a fresh tree would pay inside its own call — the tree's depth /
  * expected-visits pass (one read-back) and the first allocation of the ray-reordering scratch for batches of `n_rays_hint` rays (kept

@@ -1,0 +1,150 @@
+// TEST INFRASTRUCTURE (CPU, no GPU): compiles the text of the radius-query kernel — bvh_amd/csrc/radius_body.inc (which includes
+// closest_body.inc for the distance functions) with the device helpers of bvh_amd/csrc/trace_device.h — for the HOST and runs it with
+// one emulated lane per query (the queries of a batch one after another, or split over host threads). What it can show: the walk of
+// the very source the device runs lists the primitives a brute force over the same distance functions lists, in the tree's order, and
+// keeps to its segment; the device's counts, lists and distances must equal these bit for bit. What it cannot show: anything that
+// needs the hardware. tests/test_radius_search_host.py drives it; tests/test_gpu_radius_search.py uses it too.
+//
+// Built by the tests with: g++ -std=c++20 -O1 -mavx2 -mfma -ffp-contract=off -fno-strict-aliasing -shared -fPIC -pthread.
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "../../include/bvh_amd.h"                               // bvh_hit3f / bvh_hit3d, bvh_amd_counters, BVH_AMD_INVALID
+
+// ---- single-lane stand-ins for what hip_runtime.h provides ------------------------------------------------------------
+#define __device__
+#define __host__
+#define __global__
+#define __forceinline__ inline
+#define __launch_bounds__(x)
+#define __shared__ static
+
+struct float2 { float x, y; };
+struct float4 { float x, y, z, w; };
+struct double2 { double x, y; };
+struct uint2 { uint32_t x, y; };
+struct uint4 { uint32_t x, y, z, w; };
+inline float4 make_float4(float x, float y, float z, float w) { return {x, y, z, w}; }
+inline double2 make_double2(double x, double y) { return {x, y}; }
+inline uint32_t __float_as_uint(float x) { return __builtin_bit_cast(uint32_t, x); }
+inline float __uint_as_float(uint32_t x) { return __builtin_bit_cast(float, x); }
+inline long long __double_as_longlong(double x) { return __builtin_bit_cast(long long, x); }
+inline double __longlong_as_double(long long x) { return __builtin_bit_cast(double, x); }
+using std::min;
+
+// ---- stand-ins for bvh_amd/csrc/common.h (which needs the HIP headers) ------------------------------------------------------
+namespace bvh_amd {
+constexpr unsigned kCountBits = 4;
+constexpr uint32_t kCountMask = 15u;
+constexpr int kWave = 64;
+template <typename T> struct PairNode;
+template <> struct PairNode<float> { float lb[6], rb[6]; uint32_t li, ri; uint32_t pad[2]; };
+template <> struct PairNode<double> { double lb[6], rb[6]; uint32_t li, ri; uint32_t pad[6]; };
+template <typename T> struct HitOf;
+template <> struct HitOf<float> { using Type = bvh_hit3f; };
+template <> struct HitOf<double> { using Type = bvh_hit3d; };
+enum { LEAF_TRIANGLE = 0, LEAF_SPHERE = 1 };
+} // namespace bvh_amd
+
+#include "../../bvh_amd/csrc/trace_device.h"
+#include "../../bvh_amd/csrc/radius_body.inc"
+
+namespace {
+
+using namespace bvh_amd;
+
+template <typename T, int Leaf, bool Deep>
+void walk_range(const RadiusArgs<T>& a0, unsigned long long begin, unsigned long long end, unsigned long long (&cnt)[3]) {
+    RadiusArgs<T> a = a0;
+    std::vector<uint32_t> lds_node(size_t(kRadiusLds) * kBlock);
+    std::vector<uint32_t> deep_nodes(Deep ? a.deep_cap : 1);
+    a.deep_nodes = deep_nodes.data();                                        // one lane at a time: lane 0's spill
+    for (unsigned long long s = begin; s < end; ++s) {
+        if (a.offsets) radius_lane<T, Leaf, true, Deep, true>(a, s, lds_node.data(), 0, 0, cnt);
+        else radius_lane<T, Leaf, true, Deep, false>(a, s, lds_node.data(), 0, 0, cnt);
+    }
+}
+
+template <typename T, int Leaf>
+int walk(const void* pairs, uint32_t root_index, const void* prims, const void* queries, size_t n, const uint32_t* order, const uint32_t* prim_ids,
+         uint32_t deep_cap, int threads, uint32_t* counts, const uint64_t* offsets, uint32_t* list_prims, void* list_dist, unsigned long long* counters3) {
+    RadiusArgs<T> a{};
+    a.pairs = static_cast<const PairNode<T>*>(pairs); a.prims = static_cast<const T*>(prims); a.queries = static_cast<const T*>(queries);
+    a.counts = counts; a.offsets = reinterpret_cast<const unsigned long long*>(offsets); a.list_prims = list_prims; a.list_dist = static_cast<T*>(list_dist);
+    a.n = n; a.first = 0; a.order = order; a.prim_ids = prim_ids; a.counters = nullptr;
+    a.deep_cap = deep_cap; a.root_index = root_index;
+    const int nt = std::max(1, threads);
+    std::vector<std::thread> pool;
+    std::vector<unsigned long long> sums(3 * size_t(nt), 0);
+    for (int t = 0; t < nt; ++t) {
+        const unsigned long long b = n * t / nt, e = n * (t + 1) / nt;
+        pool.emplace_back([&, t, b, e] {
+            unsigned long long cnt[3] = {0, 0, 0};
+            if (deep_cap) walk_range<T, Leaf, true>(a, b, e, cnt); else walk_range<T, Leaf, false>(a, b, e, cnt);
+            for (int k = 0; k < 3; ++k) sums[3 * size_t(t) + k] = cnt[k];
+        });
+    }
+    for (auto& th : pool) th.join();
+    for (int k = 0; k < 3; ++k) { counters3[k] = 0; for (int t = 0; t < nt; ++t) counters3[k] += sums[3 * size_t(t) + k]; }
+    return 0;
+}
+
+template <typename T, int Leaf>
+T prim_dist2(const T* prims, size_t i, const T (&q)[3]) {
+    T u = T(0), v = T(0);
+    if (Leaf == LEAF_TRIANGLE) { T p[12]; std::memcpy(p, prims + 12 * i, sizeof(p)); return tri_dist2(p, q, u, v); }
+    T s[4]; std::memcpy(s, prims + 4 * i, sizeof(s)); return sphere_dist2(s, q);
+}
+
+// every query against every primitive through the kernel's distance function: out_d2[k * n_prims + i]
+template <typename T, int Leaf>
+void brute(const T* prims, size_t n_prims, const T* queries, size_t n, T* out_d2, int threads) {
+    const int nt = std::max(1, threads);
+    std::vector<std::thread> pool;
+    for (int t = 0; t < nt; ++t) {
+        pool.emplace_back([=] {
+            for (size_t k = n * t / nt; k < n * (t + 1) / nt; ++k) {
+                const T q[3] = { queries[4 * k], queries[4 * k + 1], queries[4 * k + 2] };
+                for (size_t i = 0; i < n_prims; ++i) out_d2[k * n_prims + i] = prim_dist2<T, Leaf>(prims, i, q);
+            }
+        });
+    }
+    for (auto& th : pool) th.join();
+}
+
+} // namespace
+
+extern "C" {
+
+// out_d2 (n x n_prims scalars of the primitives' type) = the kernel's squared distance of every query to every BVH-order primitive
+void radius_host_brute(int is_double, int leaf, const void* prims, size_t n_prims, const void* queries, size_t n, void* out_d2, int threads) {
+    if (is_double) {
+        if (leaf == LEAF_SPHERE) brute<double, LEAF_SPHERE>(static_cast<const double*>(prims), n_prims, static_cast<const double*>(queries), n, static_cast<double*>(out_d2), threads);
+        else brute<double, LEAF_TRIANGLE>(static_cast<const double*>(prims), n_prims, static_cast<const double*>(queries), n, static_cast<double*>(out_d2), threads);
+    } else {
+        if (leaf == LEAF_SPHERE) brute<float, LEAF_SPHERE>(static_cast<const float*>(prims), n_prims, static_cast<const float*>(queries), n, static_cast<float*>(out_d2), threads);
+        else brute<float, LEAF_TRIANGLE>(static_cast<const float*>(prims), n_prims, static_cast<const float*>(queries), n, static_cast<float*>(out_d2), threads);
+    }
+}
+
+// The kernel's walk for n queries {x, y, z, max_distance} (slot s reads query order[s], or s); leaf 0 = triangles, 1 = spheres;
+// prim_ids (optional) = BVH_AMD_RAY_ORIGINAL_IDS; deep_cap > 0: the HBM spill of trees deeper than 64 levels, deep_cap entries.
+// counts (optional), offsets (optional: NULL = the count-pass variant), list_prims, list_dist (optional) as in the C ABI;
+// counters3 = {pairs fetched, primitives tested, leaves visited}. With threads > 1 the queries' segments must not overlap. Returns 0.
+int radius_host_walk(int is_double, int leaf, const void* pairs, uint32_t root_index, const void* prims, const void* queries, size_t n,
+                     const uint32_t* order, const uint32_t* prim_ids, uint32_t deep_cap, int threads, uint32_t* counts, const uint64_t* offsets,
+                     uint32_t* list_prims, void* list_dist, unsigned long long* counters3) {
+    if (is_double) {
+        if (leaf == LEAF_SPHERE) return walk<double, LEAF_SPHERE>(pairs, root_index, prims, queries, n, order, prim_ids, deep_cap, threads, counts, offsets, list_prims, list_dist, counters3);
+        return walk<double, LEAF_TRIANGLE>(pairs, root_index, prims, queries, n, order, prim_ids, deep_cap, threads, counts, offsets, list_prims, list_dist, counters3);
+    }
+    if (leaf == LEAF_SPHERE) return walk<float, LEAF_SPHERE>(pairs, root_index, prims, queries, n, order, prim_ids, deep_cap, threads, counts, offsets, list_prims, list_dist, counters3);
+    return walk<float, LEAF_TRIANGLE>(pairs, root_index, prims, queries, n, order, prim_ids, deep_cap, threads, counts, offsets, list_prims, list_dist, counters3);
+}
+
+} // extern "C"

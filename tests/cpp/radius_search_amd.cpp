@@ -1,0 +1,86 @@
+// Radius queries through the C++20 mirror (bvh::v2::amd::radius_search_batch): the small deterministic mesh of closest_points_amd.cpp,
+// serial High build, permuted PrecomputedTri, a batch of queries of three radii. Prints the tree's prim ids, the offsets, then one
+// line per listed primitive "query prim distance" (the distance as a hexadecimal float: exact); tests/test_gpu_radius_search.py
+// compares them with bvh_amd.radius_search. Also runs the device form with fixed segments and checks it against the exact lists.
+#include <bvh/v2/bvh.h>
+#include <bvh/v2/vec.h>
+#include <bvh/v2/node.h>
+#include <bvh/v2/default_builder.h>
+#include <bvh/v2/tri.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+using Scalar = float;
+using Vec3 = bvh::v2::Vec<Scalar, 3>;
+using BBox = bvh::v2::BBox<Scalar, 3>;
+using Tri = bvh::v2::Tri<Scalar, 3>;
+using Node = bvh::v2::Node<Scalar, 3>;
+using Bvh = bvh::v2::Bvh<Node>;
+using Query = bvh::v2::amd::PointQuery<Scalar>;
+template <typename T> using DeviceArray = bvh::v2::amd::DeviceArray<T>;
+static_assert(sizeof(Query) == 4 * sizeof(Scalar));
+
+int main() {
+    std::vector<Tri> tris;                                    // a 12 x 12 height field, two triangles per cell
+    const int side = 12;
+    auto h = [](int i, int j) { return static_cast<Scalar>(0.1 * std::sin(0.7 * i) * std::cos(0.4 * j)); };
+    for (int i = 0; i < side; ++i)
+        for (int j = 0; j < side; ++j) {
+            const Vec3 a(Scalar(i), h(i, j), Scalar(j)), b(Scalar(i + 1), h(i + 1, j), Scalar(j));
+            const Vec3 c(Scalar(i + 1), h(i + 1, j + 1), Scalar(j + 1)), d(Scalar(i), h(i, j + 1), Scalar(j + 1));
+            tris.emplace_back(a, b, c);
+            tris.emplace_back(a, c, d);
+        }
+    std::vector<BBox> bboxes(tris.size());
+    std::vector<Vec3> centers(tris.size());
+    for (size_t i = 0; i < tris.size(); ++i) { bboxes[i] = tris[i].get_bbox(); centers[i] = tris[i].get_center(); }
+    typename bvh::v2::DefaultBuilder<Node>::Config config;
+    config.quality = bvh::v2::DefaultBuilder<Node>::Quality::High;
+    auto bvh = bvh::v2::DefaultBuilder<Node>::build(bboxes, centers, config);
+    auto prims = bvh::v2::amd::permuted_triangles(bvh, std::span<const Tri>(tris));
+
+    std::vector<Query> queries;
+    const Scalar radii[3] = { Scalar(0.25), Scalar(1.5), Scalar(INFINITY) };
+    for (int k = 0; k < 200; ++k) {
+        const Scalar x = Scalar(-1.5 + 15.0 * ((k * 37) % 200) / 200.0), y = Scalar(-1.0 + 2.0 * ((k * 53) % 200) / 200.0);
+        const Scalar z = Scalar(-1.5 + 15.0 * ((k * 91) % 200) / 200.0);
+        queries.push_back(Query{ Vec3(x, y, z), k % 50 == 49 ? radii[2] : radii[k % 2] });
+    }
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> ids;
+    std::vector<Scalar> dist;
+    bvh::v2::amd::radius_search_batch(bvh, prims, std::span<const Query>(queries), offsets, ids, &dist);
+
+    // the device form, 4 slots per query in one pass: a prefix of each exact list, the rest invalid, counts not truncated
+    const size_t n = queries.size(), k_slots = 4;
+    std::vector<uint64_t> fixed(n + 1);
+    for (size_t q = 0; q <= n; ++q) fixed[q] = k_slots * q;
+    DeviceArray<Query> d_queries{std::span<const Query>(queries)};
+    DeviceArray<uint64_t> d_fixed{std::span<const uint64_t>(fixed)};
+    DeviceArray<uint32_t> d_counts(n), d_list(k_slots * n);
+    bvh::v2::amd::radius_search_batch(bvh, prims, d_queries, &d_counts, &d_fixed, &d_list);
+    std::vector<uint32_t> counts(n), list(k_slots * n);
+    d_counts.download(std::span<uint32_t>(counts));
+    d_list.download(std::span<uint32_t>(list));
+    for (size_t q = 0; q < n; ++q) {
+        const uint64_t len = offsets[q + 1] - offsets[q];
+        if (counts[q] != len) { std::fprintf(stderr, "query %zu: count %u, exact list %llu\n", q, counts[q], static_cast<unsigned long long>(len)); return 1; }
+        for (size_t s = 0; s < k_slots; ++s) {
+            const uint32_t want = s < len ? ids[offsets[q] + s] : BVH_AMD_INVALID;
+            if (list[k_slots * q + s] != want) { std::fprintf(stderr, "query %zu slot %zu: %u, expected %u\n", q, s, list[k_slots * q + s], want); return 1; }
+        }
+    }
+
+    std::printf("prim_ids:");
+    for (size_t id : bvh.prim_ids) std::printf(" %zu", id);
+    std::printf("\noffsets:");
+    for (uint64_t o : offsets) std::printf(" %llu", static_cast<unsigned long long>(o));
+    std::printf("\n");
+    for (size_t q = 0; q < n; ++q)
+        for (uint64_t e = offsets[q]; e < offsets[q + 1]; ++e) std::printf("%zu %u %a\n", q, ids[e], double(dist[e]));
+    return 0;
+}
