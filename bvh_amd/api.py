@@ -650,6 +650,54 @@ def radius_search(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", max_p
     return out + (cnt,) if counters else out
 
 
+KNN_MAX_K = 64                                  # BVH_AMD_KNN_MAX_K
+
+
+def knn(bvh: Bvh, prims, points, k: int, max_distance: float = float("inf"), leaf: str = "tri", distances: bool = True,
+        original_ids: bool = False, sort_queries=None, counters: bool = False):
+    """For each point, the k nearest primitives within max_distance (bvhXX_knn_*), in ascending (distance, BVH-order index) order. prims
+    are in BVH order, as for closest_points; points: (n, 3) with the scalar max_distance, or (n, 4) with a per-query radius in column 3
+    (max_distance left at its default). Returns (ids, dist, counts): ids int32 (n, k), BVH-order indices (bvh.prim_ids[i] with
+    original_ids); dist (n, k) beside them (None without `distances`); counts int32 (n,), the valid entries of each row. The unused
+    slots of a row hold -1 (INVALID) and the query's max_distance. With counters, (pairs, tests, leaves) is appended to the result.
+    sort_queries: True / False force / forbid reordering the batch internally (None: the library decides)."""
+    torch = _torch()
+    if bvh.dim != 3:
+        raise TypeError("knn: 3D trees only")
+    if leaf not in ("tri", "sphere"):
+        raise ValueError("leaf is 'tri' or 'sphere'")
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k must be in [1, {KNN_MAX_K}]")
+    dt = torch.float32 if bvh._s[1] == "f" else torch.float64
+    pts = _dev(points)
+    if pts.dim() != 2 or pts.shape[1] not in (3, 4):
+        raise ValueError("points must be (n, 3) or (n, 4)")
+    if pts.dtype != dt:
+        raise TypeError("points dtype must match the BVH scalar type")
+    if pts.shape[1] == 3:
+        q = torch.empty((pts.shape[0], 4), dtype=dt, device=pts.device)
+        q[:, :3] = pts
+        q[:, 3] = float(max_distance)
+    else:
+        if max_distance != float("inf"):
+            raise ValueError("(n, 4) points carry their own radius: leave max_distance at its default")
+        q = pts
+    p = _dev(prims)
+    if p.dtype != dt:
+        raise TypeError("prims dtype must match the BVH scalar type")
+    n = q.shape[0]
+    ids = torch.empty((n, k), dtype=torch.int32, device=q.device)
+    dist = torch.empty((n, k), dtype=dt, device=q.device) if distances else None
+    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_knn_{leaf}")
+    _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, k, int(_sort_flags(sort_queries, original_ids)), ids.data_ptr(),
+                  dist.data_ptr() if distances else None, counts.data_ptr(), cnt.data_ptr() if counters else None, _stream()), "knn")
+    out = (ids, dist, counts)
+    return out + (cnt,) if counters else out
+
+
 def hits_to_numpy(hits) -> np.ndarray:
     a = hits.detach().cpu().numpy()
     return a.view(HITF if a.dtype == np.float32 else HITD).reshape(-1)

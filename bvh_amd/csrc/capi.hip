@@ -548,6 +548,18 @@ int radius_search(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims
                             static_cast<hipStream_t>(stream));
 }
 
+template <typename T>
+int knn(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned k, unsigned flags, uint32_t* d_out_prims,
+        T* d_out_dist, uint32_t* d_counts, bvh_amd_counters* d_counters, void* stream)
+{
+    if (!bvh) return fail(BVH_AMD_ERR_ARG, "knn: null bvh");
+    const BvhImpl<T>& b = *impl<T>(bvh);
+    int cur = -1;
+    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
+    if (n != 0 && cur != b.device) return fail(BVH_AMD_ERR_ARG, "knn: BVH lives on another device than the current one");
+    return launch_knn<T>(b, leaf, d_prims, d_queries4, n, k, flags, d_out_prims, d_out_dist, d_counts, d_counters, static_cast<hipStream_t>(stream));
+}
+
 // bvhXX_intersect_ray{,_any}{,_robust} (c_api/bvh.h:277-295 over bvh_impl.h:235-250): one ray, the leaves go to the caller's
 // function. The walk runs on the device (traverse.hip, ray_step_kernel); `ray` is the family's own struct.
 template <typename T, int D>
@@ -776,6 +788,12 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_radius_search_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned flags, uint32_t* counts, \
                                       const uint64_t* offsets, uint32_t* list_prims, T* list_dist, bvh_amd_counters* cnt, void* s) { \
         return radius_search<T>(b, LEAF_SPHERE, prims, queries, n, flags, counts, offsets, list_prims, list_dist, cnt, s); } \
+    int bvh##S##_knn_tri(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned k, unsigned flags, uint32_t* out_prims, \
+                         T* out_dist, uint32_t* counts, bvh_amd_counters* cnt, void* s) {                           \
+        return knn<T>(b, LEAF_TRIANGLE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }        \
+    int bvh##S##_knn_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned k, unsigned flags, uint32_t* out_prims, \
+                            T* out_dist, uint32_t* counts, bvh_amd_counters* cnt, void* s) {                        \
+        return knn<T>(b, LEAF_SPHERE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }          \
     int bvh##S##_prepare_trace(const bvh##S* b, size_t n_rays_hint, void* s) {                                      \
         if (!b) return fail(BVH_AMD_ERR_ARG, "prepare_trace: null bvh");                                            \
         int cur = -1;                                                                                               \

@@ -270,6 +270,11 @@ int launch_radius(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T*
                   const uint64_t* d_offsets, uint32_t* d_list_prims, T* d_list_dist, bvh_amd_counters* d_counters, hipStream_t stream);
 // d_offsets[0..n] = {0, c0, c0 + c1, ...}: 64-bit sums, entirely in stream order (no read-back)
 int offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets, hipStream_t stream);
+// knn.hip: batched k-nearest queries, n x {x, y, z, max_distance} -> per query a row of k {index, distance} slots in ascending
+// (distance^2, index) order, padded with {INVALID, max_distance} (flags: ORIGINAL_IDS, SORTED, UNSORTED)
+template <typename T>
+int launch_knn(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T* d_queries, size_t n, unsigned k, unsigned flags, uint32_t* d_out_prims,
+               T* d_out_dist, uint32_t* d_counts, bvh_amd_counters* d_counters, hipStream_t stream);
 void last_launch_plan(int out[4]);                            // traverse.hip: {reordered, coop, refill, leaf} of the calling thread's latest launch
 int wave_times(unsigned long long* out, size_t capacity_waves, size_t* n_waves);   // traverse.hip: developer library only
 void last_plan_search(float ns_per_ray[5], int measurements[5], unsigned* dropped);   // traverse.hip

@@ -1,0 +1,245 @@
+// Per-lane body of the batched k-nearest query (knn.hip): the k BVH-order primitives — PrecomputedTri or Sphere — nearest to a query
+// point within max_distance, as a row of k {index, distance} slots in ascending (squared distance, index) order. The distance
+// functions are those of closest_body.inc (tri_dist2 / sphere_dist2 / box_dist2), so a distance is exactly what closest_points
+// measures, and the walk is closest_lane's with the best distance replaced by the worst of the k held: k = 1 gives closest_points'
+// primitive, distance and counters. Kept as an include so that tests/cpp/knn_body_host.cpp compiles the very same text for the host
+// (one emulated lane per query). Expects what closest_body.inc expects. Compiled with -ffp-contract=off on both sides, division and
+// square root correctly rounded: host and device produce the same bits.
+#pragma once
+
+#include "closest_body.inc"
+
+namespace bvh_amd {
+
+namespace {
+
+// Stack entries of a lane held in LDS beside its candidates ({node word, box distance^2}, as closest_lane), the rest of the first 64
+// in per-lane scratch, entries beyond 64 (trees deeper than 64 levels only) in HBM.
+constexpr int kKnnLds = 8;
+constexpr int kKnnSmall = 64;
+
+template <typename T>
+struct KnnArgs {
+    const PairNode<T>* pairs;
+    const T* prims;                            // BVH order: PrecomputedTri (12 scalars) or Sphere<T, 3> (4 scalars)
+    const T* queries;                          // {x, y, z, max_distance} per query, caller order
+    uint32_t* out_prims;                       // n x k, row-major, caller order
+    T* out_dist;                               // optional: n x k, sqrt(d2) beside each listed primitive
+    uint32_t* counts;                          // optional: valid entries per row (<= k)
+    uint32_t k;                                // 1 .. BVH_AMD_KNN_MAX_K
+    unsigned long long n;                      // slots of this launch: [first, first + n)
+    unsigned long long first;
+    const uint32_t* order;                     // optional: slot -> query index (coherence sort); results are unaffected
+    const uint32_t* prim_ids;                  // optional: list prim_ids[i] instead of the BVH-order index i (BVH_AMD_RAY_ORIGINAL_IDS)
+    bvh_amd_counters* counters;                // Stats kernels only
+    uint32_t* deep_nodes;                      // Deep kernels only: deep_cap entries per lane of the launch beyond the 64 of LDS + scratch
+    T* deep_d2;
+    uint32_t deep_cap;
+    uint32_t root_index;
+};
+
+// The block's LDS, `stride` lanes wide: candidate d2 [k][stride], stack d2 [kKnnLds][stride], candidate index [k][stride], stack node
+// word [kKnnLds][stride] (the scalars first: doubles stay 8-byte aligned). Slot s of lane tid sits at s * stride + tid of its array:
+// the bank is the lane's whatever the slot, so lanes at different heap positions do not conflict.
+template <typename T>
+struct KnnLds {
+    T* cand_d2;
+    T* stack_d2;
+    uint32_t* cand_id;
+    uint32_t* stack_node;
+};
+template <typename T>
+__host__ __device__ inline size_t knn_lds_bytes(uint32_t k, uint32_t stride) { return size_t(k + kKnnLds) * stride * (sizeof(T) + sizeof(uint32_t)); }
+template <typename T>
+__host__ __device__ inline KnnLds<T> knn_lds_carve(void* base, uint32_t k, uint32_t stride) {
+    KnnLds<T> l;
+    l.cand_d2 = static_cast<T*>(base);
+    l.stack_d2 = l.cand_d2 + size_t(k) * stride;
+    l.cand_id = reinterpret_cast<uint32_t*>(l.stack_d2 + size_t(kKnnLds) * stride);
+    l.stack_node = l.cand_id + size_t(k) * stride;
+    return l;
+}
+
+// A row entry is written once, by one lane, and not read again by the launch: non-temporal, like the lists of radius_lane.
+__device__ inline void store_row(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+__device__ inline void store_row(float* p, float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+__device__ inline void store_row(double* p, double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+
+// (d2, index) pairs in lexicographic order
+template <typename T>
+__device__ inline bool knn_less(T da, uint32_t ia, T db, uint32_t ib) { return da < db || (da == db && ia < ib); }
+
+// Max-heap on (d2, index) in the lane's first m candidate slots: the pair (vd, vi) sinks from slot `hole` (whose content is dead) to
+// its place, at most log2 m steps.
+template <typename T>
+__device__ inline void knn_sift_down(T* cand_d2, uint32_t* cand_id, uint32_t stride, int tid, uint32_t hole, uint32_t m, T vd, uint32_t vi) {
+    for (;;) {
+        uint32_t c = 2 * hole + 1;
+        if (c >= m) break;
+        T cd = cand_d2[c * stride + tid];
+        uint32_t ci = cand_id[c * stride + tid];
+        if (c + 1 < m) {
+            const T rd = cand_d2[(c + 1) * stride + tid];
+            const uint32_t ri = cand_id[(c + 1) * stride + tid];
+            if (knn_less(cd, ci, rd, ri)) { cd = rd; ci = ri; ++c; }
+        }
+        if (!knn_less(vd, vi, cd, ci)) break;
+        cand_d2[hole * stride + tid] = cd;
+        cand_id[hole * stride + tid] = ci;
+        hole = c;
+    }
+    cand_d2[hole * stride + tid] = vd;
+    cand_id[hole * stride + tid] = vi;
+}
+
+template <typename T>
+__device__ inline void knn_make_heap(T* cand_d2, uint32_t* cand_id, uint32_t stride, int tid, uint32_t m) {
+    for (uint32_t h = m / 2; h-- > 0;) knn_sift_down(cand_d2, cand_id, stride, tid, h, m, cand_d2[h * stride + tid], cand_id[h * stride + tid]);
+}
+
+// One query, one lane: closest_lane's walk — depth-first, nearer child first (ties left), the farther one pushed with its box
+// distance^2 — pruned against `worst`: max_distance^2 until k candidates are held, then the d2 of the largest (d2, index) held. A
+// child or a popped entry is kept iff its box distance^2 <= worst (not <: a primitive at the same distance with a lower index must
+// stay reachable). Inside a leaf the index ascends; a primitive is accepted while fewer than k are held iff d2 <= max_distance^2,
+// afterwards iff (d2, index) is below the largest held, which it replaces. The candidates are appended unordered until the k-th
+// makes them a max-heap; a replacement is one sift-down; at the end an in-place heapsort leaves them ascending, and the row is
+// written: nothing is stored while walking, so an invalid query still pads its row. Slot `slot` of the launch (query order[slot], or
+// slot itself); `lane` indexes the HBM spill (Deep), `tid` and `stride` the LDS arrays. cnt += {pair records fetched, primitives
+// tested, leaves visited}.
+template <typename T, int Leaf, bool Stats, bool Deep>
+__device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, const KnnLds<T>& lds, uint32_t stride, int tid, unsigned long long lane,
+                                unsigned long long (&cnt)[3]) {
+    const unsigned long long qi = a.order ? a.order[slot] : slot;
+    T qq[4];
+    load_prim4(a.queries + 4ull * qi, qq);
+    const T q[3] = { qq[0], qq[1], qq[2] };
+    const T max_d = qq[3];
+    const T r2 = max_d * max_d;
+    const uint32_t k = a.k;
+    const bool valid = q[0] == q[0] && q[1] == q[1] && q[2] == q[2] && max_d >= T(0);   // NaN coordinates / radius, negative radius: empty row
+    T* const cand_d2 = lds.cand_d2;
+    uint32_t* const cand_id = lds.cand_id;
+    T worst = r2;                                             // the pruning distance^2
+    uint32_t worst_id = BVH_AMD_INVALID;                      // the index beside it, once k are held
+    uint32_t held = 0;
+
+    uint32_t spill_node[kKnnSmall - kKnnLds];
+    T spill_d2[kKnnSmall - kKnnLds];
+    uint32_t sp = 0;
+    auto deep_at = [&](uint32_t i) { return lane * a.deep_cap + (i < a.deep_cap ? i : a.deep_cap - 1); };
+    auto push = [&](uint32_t node, T d2) {
+        if (sp < kKnnLds) { lds.stack_node[sp * stride + tid] = node; lds.stack_d2[sp * stride + tid] = d2; }
+        else if (!Deep || sp < kKnnSmall) {
+            const uint32_t i = sp - kKnnLds < uint32_t(kKnnSmall - kKnnLds - 1) ? sp - kKnnLds : uint32_t(kKnnSmall - kKnnLds - 1);
+            spill_node[i] = node; spill_d2[i] = d2;
+        } else { const unsigned long long i = deep_at(sp - kKnnSmall); a.deep_nodes[i] = node; a.deep_d2[i] = d2; }
+        ++sp;
+    };
+    // the next stacked entry that can still hold something below the worst candidate (false: the walk is over)
+    auto pop = [&](uint32_t& node) -> bool {
+        while (sp > 0) {
+            --sp;
+            uint32_t e;
+            T d2;
+            if (sp < kKnnLds) { e = lds.stack_node[sp * stride + tid]; d2 = lds.stack_d2[sp * stride + tid]; }
+            else if (!Deep || sp < kKnnSmall) {
+                const uint32_t i = sp - kKnnLds < uint32_t(kKnnSmall - kKnnLds - 1) ? sp - kKnnLds : uint32_t(kKnnSmall - kKnnLds - 1);
+                e = spill_node[i]; d2 = spill_d2[i];
+            } else { const unsigned long long i = deep_at(sp - kKnnSmall); e = a.deep_nodes[i]; d2 = a.deep_d2[i]; }
+            if (d2 <= worst) { node = e; return true; }
+        }
+        return false;
+    };
+
+    uint32_t node = a.root_index;
+    bool live = valid;
+    while (live) {
+        while ((node & kCountMask) == 0) {                    // inner node: both children in one record
+            T lb[6], rb[6];
+            uint32_t li = 0, ri = 0;
+            load_pair(a.pairs + (node >> (kCountBits + 1)), lb, rb, li, ri);
+            if (Stats) ++cnt[0];
+            const T dl = box_dist2(lb, q), dr = box_dist2(rb, q);
+            const bool hl = dl <= worst, hr = dr <= worst;
+            if (hl && hr) {
+                if (dr < dl) { push(li, dl); node = ri; }
+                else { push(ri, dr); node = li; }
+            } else if (hl) node = li;
+            else if (hr) node = ri;
+            else if (!pop(node)) { live = false; break; }
+        }
+        if (!live) break;
+        const uint32_t first = node >> kCountBits, count = node & kCountMask;
+        if (Stats) ++cnt[2];
+        for (uint32_t i = first; i < first + count; ++i) {
+            if (Stats) ++cnt[1];
+            T d2, u = T(0), v = T(0);
+            if (Leaf == LEAF_TRIANGLE) {
+                T p[12];
+                load_prim12(a.prims + 12ull * i, p);
+                d2 = tri_dist2(p, q, u, v);
+            } else {
+                T s[4];
+                load_prim4(a.prims + 4ull * i, s);
+                d2 = sphere_dist2(s, q);
+            }
+            if (held < k) {
+                if (d2 <= r2) {
+                    cand_d2[held * stride + tid] = d2;
+                    cand_id[held * stride + tid] = i;
+                    if (++held == k) {
+                        knn_make_heap(cand_d2, cand_id, stride, tid, k);
+                        worst = cand_d2[tid]; worst_id = cand_id[tid];
+                    }
+                }
+            } else if (knn_less(d2, i, worst, worst_id)) {
+                knn_sift_down(cand_d2, cand_id, stride, tid, 0u, k, d2, i);
+                worst = cand_d2[tid]; worst_id = cand_id[tid];
+            }
+        }
+        live = pop(node);
+    }
+
+    // ascending (d2, index): heapsort in place
+    if (held < k) knn_make_heap(cand_d2, cand_id, stride, tid, held);
+    for (uint32_t m = held; m-- > 1;) {
+        const T ld = cand_d2[m * stride + tid], td = cand_d2[tid];
+        const uint32_t li = cand_id[m * stride + tid], ti = cand_id[tid];
+        cand_d2[m * stride + tid] = td; cand_id[m * stride + tid] = ti;
+        knn_sift_down(cand_d2, cand_id, stride, tid, 0u, m, ld, li);
+    }
+    uint32_t* const row_prims = a.out_prims + qi * k;
+    T* const row_dist = a.out_dist ? a.out_dist + qi * k : nullptr;
+    for (uint32_t j = 0; j < held; ++j) {
+        const uint32_t i = cand_id[j * stride + tid];
+        store_row(row_prims + j, a.prim_ids ? a.prim_ids[i] : i);
+        if (row_dist) store_row(row_dist + j, Num<T>::sqrt_(cand_d2[j * stride + tid]));
+    }
+    for (uint32_t j = held; j < k; ++j) {                     // the unused rest of the row: closest_points' miss record
+        store_row(row_prims + j, BVH_AMD_INVALID);
+        if (row_dist) store_row(row_dist + j, max_d);
+    }
+    if (a.counts) a.counts[qi] = held;
+}
+
+} // namespace
+
+} // namespace bvh_amd

@@ -320,6 +320,8 @@ template <> struct Api<float, 3> {
     static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3f_closest_points_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
     static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
+    static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
+    static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, float*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitorf v{ user, leaf, inner };
         return bvh3f_intersect_ray_visit(h, static_cast<const bvh_ray3f*>(ray), start, f, &v);
@@ -356,6 +358,8 @@ template <> struct Api<double, 3> {
     static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3d_closest_points_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
     static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
+    static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
+    static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, double*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitord v{ user, leaf, inner };
         return bvh3d_intersect_ray_visit(h, static_cast<const bvh_ray3d*>(ray), start, f, &v);
@@ -968,6 +972,64 @@ void radius_search_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename
                          std::vector<typename Node::Scalar>* list_dist = nullptr) {
     using T = typename Node::Scalar;
     detail::radius_host<T>(&Api<T, 3>::radius_sphere, bvh.device(), spheres.data(), queries, offsets, list_prims, list_dist, "radius_search_sphere");
+}
+
+// For each query, the k nearest primitives within its max_distance (include/bvh_amd.h: bvhXX_knn_*), k in [1, BVH_AMD_KNN_MAX_K]: row q
+// is out_prims[q * k .. q * k + k), BVH-order indices in ascending (distance, index) order, the unused slots invalid; `out_dist`
+// (optional) the distances beside them (max_distance in the unused slots); `counts` (optional) the valid entries of each row.
+namespace detail {
+template <typename T>
+using KnnFn = int (*)(const typename Api<T, 3>::Handle*, const void*, const void*, size_t, unsigned, unsigned, uint32_t*, void*, uint32_t*);
+template <typename T>
+void knn_device(KnnFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, const DeviceArray<PointQuery<T>>& queries, unsigned k,
+                DeviceArray<uint32_t>& out_prims, DeviceArray<T>* out_dist, DeviceArray<uint32_t>* counts, const char* what) {
+    const size_t n = queries.size();
+    if (out_prims.size() < n * k || (out_dist && out_dist->size() < n * k) || (counts && counts->size() < n))
+        throw Error(std::string(what) + ": rows need n * k entries, counts n");
+    check(fn(h, prims, queries.data(), n, k, 0u, out_prims.data(), out_dist ? out_dist->data() : nullptr, counts ? counts->data() : nullptr), what);
+}
+template <typename T>
+void knn_host(KnnFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, std::span<const PointQuery<T>> queries, unsigned k,
+              std::vector<uint32_t>& out_prims, std::vector<T>* out_dist, std::vector<uint32_t>* counts, const char* what) {
+    const size_t n = queries.size();
+    out_prims.assign(n * k, BVH_AMD_INVALID);
+    if (out_dist) out_dist->assign(n * k, T(0));
+    if (counts) counts->assign(n, 0u);
+    if (n == 0) return;
+    DeviceArray<PointQuery<T>> d_queries(queries);
+    DeviceArray<uint32_t> d_prims(n * k), d_counts(counts ? n : 0);
+    DeviceArray<T> d_dist(out_dist ? n * k : 0);
+    knn_device<T>(fn, h, prims, d_queries, k, d_prims, out_dist ? &d_dist : nullptr, counts ? &d_counts : nullptr, what);
+    d_prims.download(std::span<uint32_t>(out_prims));
+    if (out_dist) d_dist.download(std::span<T>(*out_dist));
+    if (counts) d_counts.download(std::span<uint32_t>(*counts));
+}
+} // namespace detail
+
+template <typename Node>
+void knn_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, const DeviceArray<PointQuery<typename Node::Scalar>>& queries,
+               unsigned k, DeviceArray<uint32_t>& out_prims, DeviceArray<typename Node::Scalar>* out_dist = nullptr, DeviceArray<uint32_t>* counts = nullptr) {
+    using T = typename Node::Scalar;
+    detail::knn_device<T>(&Api<T, 3>::knn_tri, bvh.device(), prims.data(), queries, k, out_prims, out_dist, counts, "knn_tri");
+}
+template <typename Node>
+void knn_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, const DeviceArray<PointQuery<typename Node::Scalar>>& queries,
+               unsigned k, DeviceArray<uint32_t>& out_prims, DeviceArray<typename Node::Scalar>* out_dist = nullptr, DeviceArray<uint32_t>* counts = nullptr) {
+    using T = typename Node::Scalar;
+    detail::knn_device<T>(&Api<T, 3>::knn_sphere, bvh.device(), spheres.data(), queries, k, out_prims, out_dist, counts, "knn_sphere");
+}
+// Host form: out_prims (and *out_dist) are resized to queries.size() * k, *counts to queries.size().
+template <typename Node>
+void knn_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, std::span<const PointQuery<typename Node::Scalar>> queries,
+               unsigned k, std::vector<uint32_t>& out_prims, std::vector<typename Node::Scalar>* out_dist = nullptr, std::vector<uint32_t>* counts = nullptr) {
+    using T = typename Node::Scalar;
+    detail::knn_host<T>(&Api<T, 3>::knn_tri, bvh.device(), prims.data(), queries, k, out_prims, out_dist, counts, "knn_tri");
+}
+template <typename Node>
+void knn_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, std::span<const PointQuery<typename Node::Scalar>> queries,
+               unsigned k, std::vector<uint32_t>& out_prims, std::vector<typename Node::Scalar>* out_dist = nullptr, std::vector<uint32_t>* counts = nullptr) {
+    using T = typename Node::Scalar;
+    detail::knn_host<T>(&Api<T, 3>::knn_sphere, bvh.device(), spheres.data(), queries, k, out_prims, out_dist, counts, "knn_sphere");
 }
 
 // ---- multi-GPU: rays shard, the scene is broadcast once over RCCL inside the library -------------------------------

@@ -540,6 +540,37 @@ BVH_AMD_API int bvh3d_radius_search_sphere(const struct bvh3d*, const double* d_
  * writes d_offsets[0] = 0. */
 BVH_AMD_API int bvh_amd_offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets, void* stream);
 
+/* ---- batched k-nearest queries: for each point, the k nearest primitives in ascending distance ----------------------------------- */
+/* Queries and primitives as for bvhXX_closest_points_* (n x {x, y, z, max_distance}; BVH-order PrecomputedTri or Sphere<T, 3>); k in
+ * [1, BVH_AMD_KNN_MAX_K]. With r2 = max_distance * max_distance (rounded in the scalar type), the result of a query is the k smallest
+ * pairs (d2, i), in lexicographic order, among the BVH-order indices i with d2(i) <= r2; d2 is the squared distance
+ * bvhXX_closest_points_* measures. The pairs are listed in ascending (d2, i) order: equal squared distances by ascending BVH-order
+ * index (also when BVH_AMD_RAY_ORIGINAL_IDS maps the reported ids). k = 1 is closest_points' {prim, t}.
+ *   output:  d_out_prims (n x k, row-major, caller order, required): BVH-order indices (bvh.prim_ids[i] with
+ *            BVH_AMD_RAY_ORIGINAL_IDS). d_out_dist (n x k, or NULL): sqrt(d2), correctly rounded. d_counts (n, or NULL): the valid
+ *            entries of each row, <= k. The unused slots of a row hold {BVH_AMD_INVALID, max_distance} (the miss record of
+ *            closest_points, the padding of radius_search). Nothing outside [0, n * k) of the output arrays is written.
+ *   invalid: a NaN coordinate and a negative or NaN max_distance give count 0 and a fully padded row whose distances carry the query's
+ *            own max_distance bits; +inf is unbounded; 0 yields the primitives at distance exactly 0.
+ *   walk:    that of closest_points, pruned against the worst candidate: a subtree is entered iff the squared distance of its box is
+ *            <= r2 while fewer than k candidates are held, <= the k-th smallest d2 held afterwards.
+ *   flags:   BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED as for closest_points (with neither, batches of >= 1M
+ *            queries are reordered internally). Any other bit: BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * A row depends only on the tree, the primitives and its query: not on batch size, position or order, the flags, the stream or the
+ * thread. d_counters (optional) receives {pair records fetched, primitives tested, leaves visited}. Alignment: d_prims and d_queries4
+ * 16 bytes, d_counters and a double d_out_dist 8, the rest 4. 3D trees only; k == 0 or k > BVH_AMD_KNN_MAX_K, a 2D tree, a NULL handle,
+ * NULL prims, queries or d_out_prims, a misaligned pointer and a tree without a device copy are refused with BVH_AMD_ERR_ARG.
+ * Re-entrant on a const tree (no work slot of the tree is claimed). */
+#define BVH_AMD_KNN_MAX_K 64
+BVH_AMD_API int bvh3f_knn_tri(const struct bvh3f*, const float* d_tris12, const float* d_queries4, size_t n, unsigned k, unsigned flags,
+    uint32_t* d_out_prims, float* d_out_dist, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_knn_tri(const struct bvh3d*, const double* d_tris12, const double* d_queries4, size_t n, unsigned k, unsigned flags,
+    uint32_t* d_out_prims, double* d_out_dist, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_knn_sphere(const struct bvh3f*, const float* d_sph4, const float* d_queries4, size_t n, unsigned k, unsigned flags,
+    uint32_t* d_out_prims, float* d_out_dist, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_knn_sphere(const struct bvh3d*, const double* d_sph4, const double* d_queries4, size_t n, unsigned k, unsigned flags,
+    uint32_t* d_out_prims, double* d_out_dist, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
+
 /* Optional, additive: pays NOW what the first large batch through a fresh tree would pay inside its own call — the tree's depth /
  * expected-visits pass (one read-back) and the first allocation of the ray-reordering scratch for batches of `n_rays_hint` rays (kept
  * in the library's block cache for that stream). A single Bvh::intersect on a fresh Bvh is the reference's normal use (bvh.h:160-182);
