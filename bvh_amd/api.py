@@ -517,43 +517,23 @@ def closest_points(bvh: Bvh, prims, points, max_distance: float = float("inf"), 
     barycentrics of the closest point of a triangle (point = p0 + u (p1 - p0) + v (p2 - p0); 0 for spheres); with counters also
     (pairs, tests, leaves). sort_queries: True / False force / forbid reordering the batch internally (None: the library decides)."""
     torch = _torch()
-    if bvh.dim != 3:
-        raise TypeError("closest_points: 3D trees only")
-    if leaf not in ("tri", "sphere"):
-        raise ValueError("leaf is 'tri' or 'sphere'")
-    s = bvh._s
-    dt = torch.float32 if s[1] == "f" else torch.float64
-    pts = _dev(points)
-    if pts.dim() != 2 or pts.shape[1] not in (3, 4):
-        raise ValueError("points must be (n, 3) or (n, 4)")
-    if pts.dtype != dt:
-        raise TypeError("points dtype must match the BVH scalar type")
-    if pts.shape[1] == 3:
-        q = torch.empty((pts.shape[0], 4), dtype=dt, device=pts.device)
-        q[:, :3] = pts
-        q[:, 3] = float(max_distance)
-    else:
-        if max_distance != float("inf"):
-            raise ValueError("(n, 4) points carry their own radius: leave max_distance at its default")
-        q = pts
-    p = _dev(prims)
-    if p.dtype != dt:
-        raise TypeError("prims dtype must match the BVH scalar type")
+    q, p, dt = _point_query_args(bvh, prims, points, max_distance, leaf, "closest_points", "max_distance", float("inf"))
     n = q.shape[0]
     if out is None:
         out = torch.empty((n, 4), dtype=dt, device=q.device)
     cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
-    flags = (0 if sort_queries is None else RayFlags.SORTED if sort_queries else RayFlags.UNSORTED) | (8 if original_ids else 0)
-    fn = getattr(_lib.load(), f"bvh{s}_closest_points_{leaf}")
-    _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, int(flags), out.data_ptr(), cnt.data_ptr() if counters else None, _stream()),
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_closest_points_{leaf}")
+    _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, int(_sort_flags(sort_queries, original_ids)), out.data_ptr(), cnt.data_ptr() if counters else None, _stream()),
                "closest_points")
     if counters:
         return out, cnt
     return out
 
 
-def _radius_args(bvh: Bvh, prims, points, radius, leaf: str, who: str):
-    """The checks and the (n, 4) query tensor closest_points makes, for the radius queries: (queries, prims, scalar dtype)."""
+def _point_query_args(bvh: Bvh, prims, points, radius, leaf: str, who: str, name: str = "radius", unset=None):
+    """The checks and the (n, 4) query tensor of the point queries: (queries, prims, scalar dtype). `radius` is the argument called
+    `name`, `unset` its default: (n, 4) points carry a radius per query and want it left there; (n, 3) points take the scalar, which
+    must be given when the default is None."""
     torch = _torch()
     if bvh.dim != 3:
         raise TypeError(f"{who}: 3D trees only")
@@ -566,14 +546,14 @@ def _radius_args(bvh: Bvh, prims, points, radius, leaf: str, who: str):
     if pts.dtype != dt:
         raise TypeError("points dtype must match the BVH scalar type")
     if pts.shape[1] == 3:
-        if radius is None:
+        if unset is None and radius is None:
             raise ValueError("(n, 3) points need a radius")
         q = torch.empty((pts.shape[0], 4), dtype=dt, device=pts.device)
         q[:, :3] = pts
         q[:, 3] = float(radius)
     else:
-        if radius is not None:
-            raise ValueError("(n, 4) points carry their own radius: leave radius at its default")
+        if (radius is not None) if unset is None else (radius != unset):
+            raise ValueError(f"(n, 4) points carry their own radius: leave {name} at its default")
         q = pts
     p = _dev(prims)
     if p.dtype != dt:
@@ -601,7 +581,7 @@ def radius_count(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", sort_q
     """For each point, how many primitives lie within the radius (bvhXX_radius_search_* without lists): an int32 (n,) tensor; with
     counters also (pairs, tests, leaves). points: (n, 3) with the scalar radius, or (n, 4) with a per-query radius in column 3."""
     torch = _torch()
-    q, p, _ = _radius_args(bvh, prims, points, radius, leaf, "radius_count")
+    q, p, _ = _point_query_args(bvh, prims, points, radius, leaf, "radius_count")
     n = q.shape[0]
     counts = torch.zeros(n, dtype=torch.int32, device=q.device)
     cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
@@ -624,7 +604,7 @@ def radius_search(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", max_p
         overflowed.
     With counters, (pairs, tests, leaves) of the pass that wrote the lists is appended to the result."""
     torch = _torch()
-    q, p, dt = _radius_args(bvh, prims, points, radius, leaf, "radius_search")
+    q, p, dt = _point_query_args(bvh, prims, points, radius, leaf, "radius_search")
     n = q.shape[0]
     dev = q.device
     fn = getattr(_lib.load(), f"bvh{bvh._s}_radius_search_{leaf}")
@@ -662,30 +642,10 @@ def knn(bvh: Bvh, prims, points, k: int, max_distance: float = float("inf"), lea
     slots of a row hold -1 (INVALID) and the query's max_distance. With counters, (pairs, tests, leaves) is appended to the result.
     sort_queries: True / False force / forbid reordering the batch internally (None: the library decides)."""
     torch = _torch()
-    if bvh.dim != 3:
-        raise TypeError("knn: 3D trees only")
-    if leaf not in ("tri", "sphere"):
-        raise ValueError("leaf is 'tri' or 'sphere'")
     k = int(k)
     if not 1 <= k <= KNN_MAX_K:
         raise ValueError(f"k must be in [1, {KNN_MAX_K}]")
-    dt = torch.float32 if bvh._s[1] == "f" else torch.float64
-    pts = _dev(points)
-    if pts.dim() != 2 or pts.shape[1] not in (3, 4):
-        raise ValueError("points must be (n, 3) or (n, 4)")
-    if pts.dtype != dt:
-        raise TypeError("points dtype must match the BVH scalar type")
-    if pts.shape[1] == 3:
-        q = torch.empty((pts.shape[0], 4), dtype=dt, device=pts.device)
-        q[:, :3] = pts
-        q[:, 3] = float(max_distance)
-    else:
-        if max_distance != float("inf"):
-            raise ValueError("(n, 4) points carry their own radius: leave max_distance at its default")
-        q = pts
-    p = _dev(prims)
-    if p.dtype != dt:
-        raise TypeError("prims dtype must match the BVH scalar type")
+    q, p, dt = _point_query_args(bvh, prims, points, max_distance, leaf, "knn", "max_distance", float("inf"))
     n = q.shape[0]
     ids = torch.empty((n, k), dtype=torch.int32, device=q.device)
     dist = torch.empty((n, k), dtype=dt, device=q.device) if distances else None

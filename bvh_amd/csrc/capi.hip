@@ -523,28 +523,34 @@ int intersect(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, co
                               static_cast<hipStream_t>(stream));
 }
 
+// The tree behind a point query `who` (closest_points, radius_search, knn): it must live on the current device, unless the batch is empty.
+template <typename T>
+int point_query_tree(const typename CTypes<T>::Bvh* bvh, size_t n, const char* who, const BvhImpl<T>** b)
+{
+    if (!bvh) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": null bvh");
+    *b = impl<T>(bvh);
+    int cur = -1;
+    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
+    if (n != 0 && cur != (*b)->device) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH lives on another device than the current one");
+    return BVH_AMD_OK;
+}
+
 template <typename T>
 int closest(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned flags,
             typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, void* stream)
 {
-    if (!bvh) return fail(BVH_AMD_ERR_ARG, "closest_points: null bvh");
-    const BvhImpl<T>& b = *impl<T>(bvh);
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (n != 0 && cur != b.device) return fail(BVH_AMD_ERR_ARG, "closest_points: BVH lives on another device than the current one");
-    return launch_closest<T>(b, leaf, d_prims, d_queries4, n, flags, d_hits, d_counters, static_cast<hipStream_t>(stream));
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, n, "closest_points", &b)) return rc;
+    return launch_closest<T>(*b, leaf, d_prims, d_queries4, n, flags, d_hits, d_counters, static_cast<hipStream_t>(stream));
 }
 
 template <typename T>
 int radius_search(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned flags, uint32_t* d_counts,
                   const uint64_t* d_offsets, uint32_t* d_list_prims, T* d_list_dist, bvh_amd_counters* d_counters, void* stream)
 {
-    if (!bvh) return fail(BVH_AMD_ERR_ARG, "radius_search: null bvh");
-    const BvhImpl<T>& b = *impl<T>(bvh);
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (n != 0 && cur != b.device) return fail(BVH_AMD_ERR_ARG, "radius_search: BVH lives on another device than the current one");
-    return launch_radius<T>(b, leaf, d_prims, d_queries4, n, flags, d_counts, d_offsets, d_list_prims, d_list_dist, d_counters,
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, n, "radius_search", &b)) return rc;
+    return launch_radius<T>(*b, leaf, d_prims, d_queries4, n, flags, d_counts, d_offsets, d_list_prims, d_list_dist, d_counters,
                             static_cast<hipStream_t>(stream));
 }
 
@@ -552,12 +558,9 @@ template <typename T>
 int knn(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned k, unsigned flags, uint32_t* d_out_prims,
         T* d_out_dist, uint32_t* d_counts, bvh_amd_counters* d_counters, void* stream)
 {
-    if (!bvh) return fail(BVH_AMD_ERR_ARG, "knn: null bvh");
-    const BvhImpl<T>& b = *impl<T>(bvh);
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (n != 0 && cur != b.device) return fail(BVH_AMD_ERR_ARG, "knn: BVH lives on another device than the current one");
-    return launch_knn<T>(b, leaf, d_prims, d_queries4, n, k, flags, d_out_prims, d_out_dist, d_counts, d_counters, static_cast<hipStream_t>(stream));
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, n, "knn", &b)) return rc;
+    return launch_knn<T>(*b, leaf, d_prims, d_queries4, n, k, flags, d_out_prims, d_out_dist, d_counts, d_counters, static_cast<hipStream_t>(stream));
 }
 
 // bvhXX_intersect_ray{,_any}{,_robust} (c_api/bvh.h:277-295 over bvh_impl.h:235-250): one ray, the leaves go to the caller's

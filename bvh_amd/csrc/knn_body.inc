@@ -1,41 +1,28 @@
 // Per-lane body of the batched k-nearest query (knn.hip): the k BVH-order primitives — PrecomputedTri or Sphere — nearest to a query
 // point within max_distance, as a row of k {index, distance} slots in ascending (squared distance, index) order. The distance
-// functions are those of closest_body.inc (tri_dist2 / sphere_dist2 / box_dist2), so a distance is exactly what closest_points
+// functions are point_walk.inc's (tri_dist2 / sphere_dist2 / box_dist2), so a distance is exactly what closest_points
 // measures, and the walk is closest_lane's with the best distance replaced by the worst of the k held: k = 1 gives closest_points'
 // primitive, distance and counters. Kept as an include so that tests/cpp/knn_body_host.cpp compiles the very same text for the host
-// (one emulated lane per query). Expects what closest_body.inc expects. Compiled with -ffp-contract=off on both sides, division and
-// square root correctly rounded: host and device produce the same bits.
+// (one emulated lane per query). Expects what point_walk.inc expects.
 #pragma once
 
-#include "closest_body.inc"
+#include "point_walk.inc"
 
 namespace bvh_amd {
 
 namespace {
 
-// Stack entries of a lane held in LDS beside its candidates ({node word, box distance^2}, as closest_lane), the rest of the first 64
-// in per-lane scratch, entries beyond 64 (trees deeper than 64 levels only) in HBM.
+// Stack entries of a lane held in LDS beside its candidates ({node word, box distance^2}, as closest_lane), the rest in scratch and
+// HBM (point_walk.inc has the tiers).
 constexpr int kKnnLds = 8;
-constexpr int kKnnSmall = 64;
 
 template <typename T>
-struct KnnArgs {
-    const PairNode<T>* pairs;
-    const T* prims;                            // BVH order: PrecomputedTri (12 scalars) or Sphere<T, 3> (4 scalars)
-    const T* queries;                          // {x, y, z, max_distance} per query, caller order
+struct KnnArgs : PointArgs<T> {
     uint32_t* out_prims;                       // n x k, row-major, caller order
     T* out_dist;                               // optional: n x k, sqrt(d2) beside each listed primitive
     uint32_t* counts;                          // optional: valid entries per row (<= k)
+    T* deep_d2;                                // Deep kernels only: beside deep_nodes
     uint32_t k;                                // 1 .. BVH_AMD_KNN_MAX_K
-    unsigned long long n;                      // slots of this launch: [first, first + n)
-    unsigned long long first;
-    const uint32_t* order;                     // optional: slot -> query index (coherence sort); results are unaffected
-    const uint32_t* prim_ids;                  // optional: list prim_ids[i] instead of the BVH-order index i (BVH_AMD_RAY_ORIGINAL_IDS)
-    bvh_amd_counters* counters;                // Stats kernels only
-    uint32_t* deep_nodes;                      // Deep kernels only: deep_cap entries per lane of the launch beyond the 64 of LDS + scratch
-    T* deep_d2;
-    uint32_t deep_cap;
-    uint32_t root_index;
 };
 
 // The block's LDS, `stride` lanes wide: candidate d2 [k][stride], stack d2 [kKnnLds][stride], candidate index [k][stride], stack node
@@ -58,29 +45,6 @@ __host__ __device__ inline KnnLds<T> knn_lds_carve(void* base, uint32_t k, uint3
     l.cand_id = reinterpret_cast<uint32_t*>(l.stack_d2 + size_t(kKnnLds) * stride);
     l.stack_node = l.cand_id + size_t(k) * stride;
     return l;
-}
-
-// A row entry is written once, by one lane, and not read again by the launch: non-temporal, like the lists of radius_lane.
-__device__ inline void store_row(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ inline void store_row(float* p, float v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ inline void store_row(double* p, double v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 // (d2, index) pairs in lexicographic order
@@ -127,30 +91,24 @@ __device__ inline void knn_make_heap(T* cand_d2, uint32_t* cand_id, uint32_t str
 template <typename T, int Leaf, bool Stats, bool Deep>
 __device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, const KnnLds<T>& lds, uint32_t stride, int tid, unsigned long long lane,
                                 unsigned long long (&cnt)[3]) {
-    const unsigned long long qi = a.order ? a.order[slot] : slot;
-    T qq[4];
-    load_prim4(a.queries + 4ull * qi, qq);
-    const T q[3] = { qq[0], qq[1], qq[2] };
-    const T max_d = qq[3];
+    unsigned long long qi;
+    T q[3], max_d;
+    const bool valid = load_query(a, slot, qi, q, max_d);    // NaN coordinates / radius, negative radius: empty row
     const T r2 = max_d * max_d;
     const uint32_t k = a.k;
-    const bool valid = q[0] == q[0] && q[1] == q[1] && q[2] == q[2] && max_d >= T(0);   // NaN coordinates / radius, negative radius: empty row
     T* const cand_d2 = lds.cand_d2;
     uint32_t* const cand_id = lds.cand_id;
     T worst = r2;                                             // the pruning distance^2
     uint32_t worst_id = BVH_AMD_INVALID;                      // the index beside it, once k are held
     uint32_t held = 0;
 
-    uint32_t spill_node[kKnnSmall - kKnnLds];
-    T spill_d2[kKnnSmall - kKnnLds];
+    uint32_t spill_node[kPointSmall - kKnnLds];
+    T spill_d2[kPointSmall - kKnnLds];
     uint32_t sp = 0;
-    auto deep_at = [&](uint32_t i) { return lane * a.deep_cap + (i < a.deep_cap ? i : a.deep_cap - 1); };
     auto push = [&](uint32_t node, T d2) {
         if (sp < kKnnLds) { lds.stack_node[sp * stride + tid] = node; lds.stack_d2[sp * stride + tid] = d2; }
-        else if (!Deep || sp < kKnnSmall) {
-            const uint32_t i = sp - kKnnLds < uint32_t(kKnnSmall - kKnnLds - 1) ? sp - kKnnLds : uint32_t(kKnnSmall - kKnnLds - 1);
-            spill_node[i] = node; spill_d2[i] = d2;
-        } else { const unsigned long long i = deep_at(sp - kKnnSmall); a.deep_nodes[i] = node; a.deep_d2[i] = d2; }
+        else if (!Deep || sp < kPointSmall) { const uint32_t i = stack_small_at<kKnnLds>(sp); spill_node[i] = node; spill_d2[i] = d2; }
+        else { const unsigned long long i = stack_deep_at(a, lane, sp); a.deep_nodes[i] = node; a.deep_d2[i] = d2; }
         ++sp;
     };
     // the next stacked entry that can still hold something below the worst candidate (false: the walk is over)
@@ -160,10 +118,8 @@ __device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, co
             uint32_t e;
             T d2;
             if (sp < kKnnLds) { e = lds.stack_node[sp * stride + tid]; d2 = lds.stack_d2[sp * stride + tid]; }
-            else if (!Deep || sp < kKnnSmall) {
-                const uint32_t i = sp - kKnnLds < uint32_t(kKnnSmall - kKnnLds - 1) ? sp - kKnnLds : uint32_t(kKnnSmall - kKnnLds - 1);
-                e = spill_node[i]; d2 = spill_d2[i];
-            } else { const unsigned long long i = deep_at(sp - kKnnSmall); e = a.deep_nodes[i]; d2 = a.deep_d2[i]; }
+            else if (!Deep || sp < kPointSmall) { const uint32_t i = stack_small_at<kKnnLds>(sp); e = spill_node[i]; d2 = spill_d2[i]; }
+            else { const unsigned long long i = stack_deep_at(a, lane, sp); e = a.deep_nodes[i]; d2 = a.deep_d2[i]; }
             if (d2 <= worst) { node = e; return true; }
         }
         return false;
@@ -191,16 +147,8 @@ __device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, co
         if (Stats) ++cnt[2];
         for (uint32_t i = first; i < first + count; ++i) {
             if (Stats) ++cnt[1];
-            T d2, u = T(0), v = T(0);
-            if (Leaf == LEAF_TRIANGLE) {
-                T p[12];
-                load_prim12(a.prims + 12ull * i, p);
-                d2 = tri_dist2(p, q, u, v);
-            } else {
-                T s[4];
-                load_prim4(a.prims + 4ull * i, s);
-                d2 = sphere_dist2(s, q);
-            }
+            T u = T(0), v = T(0);
+            const T d2 = leaf_dist2<T, Leaf>(a.prims, i, q, u, v);
             if (held < k) {
                 if (d2 <= r2) {
                     cand_d2[held * stride + tid] = d2;
@@ -230,12 +178,12 @@ __device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, co
     T* const row_dist = a.out_dist ? a.out_dist + qi * k : nullptr;
     for (uint32_t j = 0; j < held; ++j) {
         const uint32_t i = cand_id[j * stride + tid];
-        store_row(row_prims + j, a.prim_ids ? a.prim_ids[i] : i);
-        if (row_dist) store_row(row_dist + j, Num<T>::sqrt_(cand_d2[j * stride + tid]));
+        store_stream(row_prims + j, a.prim_ids ? a.prim_ids[i] : i);
+        if (row_dist) store_stream(row_dist + j, Num<T>::sqrt_(cand_d2[j * stride + tid]));
     }
     for (uint32_t j = held; j < k; ++j) {                     // the unused rest of the row: closest_points' miss record
-        store_row(row_prims + j, BVH_AMD_INVALID);
-        if (row_dist) store_row(row_dist + j, max_d);
+        store_stream(row_prims + j, BVH_AMD_INVALID);
+        if (row_dist) store_stream(row_dist + j, max_d);
     }
     if (a.counts) a.counts[qi] = held;
 }

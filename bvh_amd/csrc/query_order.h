@@ -1,6 +1,7 @@
-// Reading order of a batch of point queries {x, y, z, max_distance} (closest.hip, radius.hip): the queries sorted by the Hilbert cell
-// of each point in the root box (ray_key.h, radix sort), so that neighbouring lanes walk the same records. One copy for both kinds of
-// query. Expects common.h, trace_device.h and ray_key.h to have been included.
+// Reading order of a batch of point queries {x, y, z, max_distance} (closest.hip, radius.hip, knn.hip, through point_query.h): the
+// queries sorted by the Hilbert cell of each point in the root box (ray_key.h, radix sort), so that neighbouring lanes walk the same
+// records. One copy for the three kinds of query (closest_keys_kernel is named after the first).
+// Expects common.h, trace_device.h and ray_key.h to have been included.
 #pragma once
 
 #include <algorithm>

@@ -1,14 +1,14 @@
 // Batched radius queries for gfx950: for every query point {x, y, z, max_distance}, how many BVH-order primitives (PrecomputedTri or
 // Sphere<T, 3>) lie within max_distance of it and, optionally, which ones, at what distance. The per-lane walk is radius_body.inc
-// (shared with the host test harness, tests/cpp/radius_body_host.cpp), the distance functions are closest_body.inc's; this file holds
-// the kernels and the launch.
+// (shared with the host test harness, tests/cpp/radius_body_host.cpp) over point_walk.inc (distance functions, stack); the launch path
+// is point_query.h's; this file holds the kernel, what is specific to the query, and the offsets scan.
 //
 // MI355X mapping:
 //   * one lane per query, one-shot grid of ceil(n / 256) blocks: no ticket counter, so no work slot of the tree is claimed and any
 //     number of launches of one const tree may run at once;
 //   * depth-first walk over the 64 / 128-byte pair records (common.h: PairNode), left child first, the right one stacked as a bare node
 //     word when both boxes are within the radius. Nothing is pruned against what was found: the list of a query is fixed by the tree;
-//   * the stack: kRadiusLds entries in LDS, the rest of 64 in per-lane scratch, beyond 64 (deep trees) in HBM;
+//   * the stack: kRadiusLds entries in LDS, the rest of 64 in per-lane scratch, beyond 64 (deep trees) in HBM (point_walk.inc);
 //   * variable-length output without a second walk inside the kernel: a query writes into [offsets[q], offsets[q + 1]) of the list
 //     arrays, never past it, pads what it does not use and reports its untruncated count. Count pass (no offsets: the Fill = false
 //     kernels hold no list store and no offset load), bvh_amd_offsets_from_counts, fill pass give exact lists; fixed-size segments
@@ -23,9 +23,7 @@
 #include "ray_key.h"
 #include "query_order.h"
 #include "radius_body.inc"
-
-#include <algorithm>
-#include <string>
+#include "point_query.h"
 
 namespace bvh_amd {
 
@@ -38,48 +36,8 @@ __global__ void __launch_bounds__(kBlock) radius_kernel(RadiusArgs<T> a) {
     const unsigned long long lane = static_cast<unsigned long long>(blockIdx.x) * kBlock + tid;
     unsigned long long cnt[3] = {0, 0, 0};
     if (lane < a.n) radius_lane<T, Leaf, Stats, Deep, Fill>(a, a.first + lane, lds_node, tid, lane, cnt);
-    if (Stats) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            cnt[0] += __shfl_down(cnt[0], off);
-            cnt[1] += __shfl_down(cnt[1], off);
-            cnt[2] += __shfl_down(cnt[2], off);
-        }
-        if ((tid & (kWave - 1)) == 0) {
-            atomicAdd(&a.counters->node_pairs, cnt[0]);
-            atomicAdd(&a.counters->prim_tests, cnt[1]);
-            atomicAdd(&a.counters->leaves, cnt[2]);
-        }
-    }
+    if (Stats) add_counters(a.counters, cnt, tid);
 }
-
-// The thresholds of closest.hip (kClosestSortMin, kClosestDeepBytes, kClosestMaxLaunch), by the same reasoning; the sort threshold
-// has not been measured for radius queries ("Radius queries").
-constexpr size_t kRadiusSortMin = size_t{1} << 20;
-constexpr size_t kRadiusDeepBytes = size_t{256} << 20;
-constexpr size_t kRadiusMaxLaunch = size_t{1} << 30;
-constexpr int kRadiusKeyBits = 7;
-
-template <typename T, int Leaf, bool Stats, bool Deep, bool Fill>
-int launch_radius_variant(const RadiusArgs<T>& a, hipStream_t stream) {
-    const unsigned long long blocks = (a.n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((radius_kernel<T, Leaf, Stats, Deep, Fill>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a);
-    BVH_HIP_TRY(hipGetLastError(), BVH_AMD_ERR_HIP);
-    return BVH_AMD_OK;
-}
-
-template <typename T, int Leaf, bool Fill>
-int launch_radius_fill(const RadiusArgs<T>& a, bool stats, bool deep, hipStream_t stream) {
-    if (deep) return stats ? launch_radius_variant<T, Leaf, true, true, Fill>(a, stream) : launch_radius_variant<T, Leaf, false, true, Fill>(a, stream);
-    return stats ? launch_radius_variant<T, Leaf, true, false, Fill>(a, stream) : launch_radius_variant<T, Leaf, false, false, Fill>(a, stream);
-}
-
-template <typename T, int Leaf>
-int launch_radius_kind(const RadiusArgs<T>& a, bool stats, bool deep, hipStream_t stream) {
-    return a.offsets ? launch_radius_fill<T, Leaf, true>(a, stats, deep, stream) : launch_radius_fill<T, Leaf, false>(a, stats, deep, stream);
-}
-
-bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
 
 // ---- offsets[0..n] = exclusive sums of counts[0..n), 64-bit, in stream order ----------------------------------------------------
 // Blocks of 4096 counts: their sums, one block that scans the sums in place, then every block scans its own counts from its base.
@@ -168,71 +126,23 @@ int offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets,
 template <typename T>
 int launch_radius(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T* d_queries, size_t n, unsigned flags, uint32_t* d_counts,
                   const uint64_t* d_offsets, uint32_t* d_list_prims, T* d_list_dist, bvh_amd_counters* d_counters, hipStream_t stream) {
-    constexpr unsigned kAccepted = BVH_AMD_RAY_ORIGINAL_IDS | BVH_AMD_RAY_SORTED | BVH_AMD_RAY_UNSORTED;
-    if (flags & ~kAccepted) return fail(BVH_AMD_ERR_ARG, "radius_search: unsupported flags (ORIGINAL_IDS, SORTED and UNSORTED only)");
-    if (n == 0) return BVH_AMD_OK;
-    if (b.dim != 3) return fail(BVH_AMD_ERR_ARG, "radius_search: 3D trees only");
-    if (!d_prims || !d_queries) return fail(BVH_AMD_ERR_ARG, "radius_search: null device pointer");
-    if (!d_counts && !d_offsets) return fail(BVH_AMD_ERR_ARG, "radius_search: at least one of d_counts and d_offsets is required");
-    if (d_offsets && !d_list_prims) return fail(BVH_AMD_ERR_ARG, "radius_search: d_offsets needs d_list_prims");
-    if (!d_offsets && (d_list_prims || d_list_dist)) return fail(BVH_AMD_ERR_ARG, "radius_search: lists need d_offsets");
-    if (misaligned(d_prims, 16) || misaligned(d_queries, 16) || misaligned(d_offsets, 8) || misaligned(d_counters, 8) || misaligned(d_counts, 4) ||
-        misaligned(d_list_prims, 4) || misaligned(d_list_dist, sizeof(T)))
-        return fail(BVH_AMD_ERR_ARG, "radius_search: device pointers must be aligned (prims and queries 16 bytes, offsets and counters 8, "
-                                     "counts, list prims and list distances to their element)");
-    if (b.node_count == 0 || !b.d_work || (b.pair_count && !b.d_pairs)) return fail(BVH_AMD_ERR_ARG, "radius_search: BVH has no device copy");
-    if ((flags & BVH_AMD_RAY_ORIGINAL_IDS) && !b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, "radius_search: BVH has no device prim ids");
-
-    StreamScope scope(stream);
-    void* deep_mem = nullptr;
-    void* sort_mem = nullptr;
-    ScratchTag deep_tag, sort_tag;
-    auto release = [&](int rc) {
-        if (deep_mem) scratch_free(deep_mem, deep_tag);
-        if (sort_mem) scratch_free(sort_mem, sort_tag);
-        return rc;
-    };
-    if (d_counters) BVH_HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(bvh_amd_counters), stream), BVH_AMD_ERR_HIP);
-
-    RadiusArgs<T> a{};
-    a.pairs = b.d_pairs; a.prims = d_prims; a.queries = d_queries;
-    a.counts = d_counts; a.offsets = reinterpret_cast<const unsigned long long*>(d_offsets); a.list_prims = d_list_prims; a.list_dist = d_list_dist;
-    a.order = nullptr; a.prim_ids = (flags & BVH_AMD_RAY_ORIGINAL_IDS) ? b.d_prim_ids : nullptr;
-    a.counters = d_counters; a.root_index = b.root_index;
-    a.deep_nodes = nullptr; a.deep_cap = 0;
-
-    // trees of more than 64 levels: an HBM spill of (depth - 64 + 1) node words per lane, launches cut to fit kRadiusDeepBytes
-    size_t per_launch = std::min(n, kRadiusMaxLaunch);
-    {
-        const int rc = tree_depth<T>(b, stream);
-        if (rc) return release(rc);
-        const int max_depth = b.max_depth.load();
-        if (max_depth > kRadiusSmall) {
-            const size_t cap = static_cast<size_t>(max_depth - kRadiusSmall + 1);
-            per_launch = std::max<size_t>(kBlock, kRadiusDeepBytes / (cap * sizeof(uint32_t)) / kBlock * kBlock);
-            per_launch = std::min(per_launch, (std::min(n, kRadiusMaxLaunch) + kBlock - 1) / kBlock * kBlock);
-            const hipError_t e = scratch_alloc(&deep_mem, per_launch * cap * sizeof(uint32_t), &deep_tag);
-            if (e != hipSuccess) { deep_mem = nullptr; return release(fail(BVH_AMD_ERR_HIP, std::string("radius_search: stack spill buffer: ") + hipGetErrorString(e))); }
-            a.deep_nodes = static_cast<uint32_t*>(deep_mem);
-            a.deep_cap = static_cast<uint32_t>(cap);
-        }
-    }
-
-    const bool reorder = n < (size_t{1} << 31) && ((flags & BVH_AMD_RAY_SORTED) ? n > 1 : (flags & BVH_AMD_RAY_UNSORTED) ? false : n >= kRadiusSortMin);
-    if (reorder) {
-        const int rc = query_order<T>(b, d_queries, n, kRadiusKeyBits, "radius_search", stream, &sort_mem, &sort_tag, &a.order);
-        if (rc) return release(rc);
-    }
-
-    const bool stats = d_counters != nullptr, deep = a.deep_cap != 0;
-    for (size_t first = 0; first < n; first += per_launch) {
-        a.first = first;
-        a.n = std::min(per_launch, n - first);
-        const int rc = leaf_kind == LEAF_TRIANGLE ? launch_radius_kind<T, LEAF_TRIANGLE>(a, stats, deep, stream)
-                                                  : launch_radius_kind<T, LEAF_SPHERE>(a, stats, deep, stream);
-        if (rc) return release(rc);
-    }
-    return release(BVH_AMD_OK);
+    const bool aligned = !(misaligned(d_prims, 16) || misaligned(d_queries, 16) || misaligned(d_offsets, 8) || misaligned(d_counters, 8) ||
+                           misaligned(d_counts, 4) || misaligned(d_list_prims, 4) || misaligned(d_list_dist, sizeof(T)));
+    const char* fault = !d_counts && !d_offsets                       ? "at least one of d_counts and d_offsets is required"
+                        : d_offsets && !d_list_prims                  ? "d_offsets needs d_list_prims"
+                        : !d_offsets && (d_list_prims || d_list_dist) ? "lists need d_offsets"
+                        : !aligned ? "device pointers must be aligned (prims and queries 16 bytes, offsets and counters 8, "
+                                     "counts, list prims and list distances to their element)"
+                                   : nullptr;
+    if (const int rc = point_query_check(b, n, flags, d_prims && d_queries, fault, "radius_search"); rc || n == 0) return rc;
+    return point_query_run<T>(b, d_prims, d_queries, n, flags, d_counters, sizeof(uint32_t), kBlock, kPointSortMin, kPointKeyBits, "radius_search", stream,
+                              [&](const PointArgs<T>& args, T*) {
+        const RadiusArgs<T> a{args, d_counts, reinterpret_cast<const unsigned long long*>(d_offsets), d_list_prims, d_list_dist};
+        return point_query_dispatch(leaf_kind, d_counters != nullptr, a.deep_cap != 0, [&](auto leaf, auto stats, auto deep) {
+            return a.offsets ? point_query_launch(radius_kernel<T, leaf(), stats(), deep(), true>, a, kBlock, 0, stream)
+                             : point_query_launch(radius_kernel<T, leaf(), stats(), deep(), false>, a, kBlock, 0, stream);
+        });
+    });
 }
 
 template int launch_radius<float>(const BvhImpl<float>&, int, const float*, const float*, size_t, unsigned, uint32_t*, const uint64_t*, uint32_t*, float*,

@@ -1,0 +1,51 @@
+// TEST INFRASTRUCTURE (CPU, no GPU): what the host harnesses of the point queries (closest_body_host.cpp, radius_body_host.cpp,
+// knn_body_host.cpp) put in front of the kernels' text: single-lane stand-ins for hip_runtime.h and for bvh_amd/csrc/common.h, then the
+// device helpers of bvh_amd/csrc/trace_device.h. The stand-ins must follow common.h (PairNode, kCountBits, LEAF_*).
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "../../include/bvh_amd.h"                               // bvh_hit3f / bvh_hit3d, bvh_amd_counters, BVH_AMD_INVALID
+
+// ---- single-lane stand-ins for what hip_runtime.h provides ------------------------------------------------------------
+#define __device__
+#define __host__
+#define __global__
+#define __forceinline__ inline
+#define __launch_bounds__(x)
+#define __shared__ static
+
+struct float2 { float x, y; };
+struct float4 { float x, y, z, w; };
+struct double2 { double x, y; };
+struct uint2 { uint32_t x, y; };
+struct uint4 { uint32_t x, y, z, w; };
+inline float4 make_float4(float x, float y, float z, float w) { return {x, y, z, w}; }
+inline double2 make_double2(double x, double y) { return {x, y}; }
+inline uint32_t __float_as_uint(float x) { return __builtin_bit_cast(uint32_t, x); }
+inline float __uint_as_float(uint32_t x) { return __builtin_bit_cast(float, x); }
+inline long long __double_as_longlong(double x) { return __builtin_bit_cast(long long, x); }
+inline double __longlong_as_double(long long x) { return __builtin_bit_cast(double, x); }
+using std::min;
+
+// ---- stand-ins for bvh_amd/csrc/common.h (which needs the HIP headers) ------------------------------------------------------
+namespace bvh_amd {
+constexpr unsigned kCountBits = 4;
+constexpr uint32_t kCountMask = 15u;
+constexpr int kWave = 64;
+template <typename T> struct PairNode;
+template <> struct PairNode<float> { float lb[6], rb[6]; uint32_t li, ri; uint32_t pad[2]; };
+template <> struct PairNode<double> { double lb[6], rb[6]; uint32_t li, ri; uint32_t pad[6]; };
+template <typename T> struct HitOf;
+template <> struct HitOf<float> { using Type = bvh_hit3f; };
+template <> struct HitOf<double> { using Type = bvh_hit3d; };
+enum { LEAF_TRIANGLE = 0, LEAF_SPHERE = 1 };
+} // namespace bvh_amd
+
+#include "../../bvh_amd/csrc/trace_device.h"

@@ -1,57 +1,12 @@
-// TEST INFRASTRUCTURE (CPU, no GPU): compiles the text of the radius-query kernel — bvh_amd/csrc/radius_body.inc (which includes
-// closest_body.inc for the distance functions) with the device helpers of bvh_amd/csrc/trace_device.h — for the HOST and runs it with
+// TEST INFRASTRUCTURE (CPU, no GPU): compiles the text of the radius-query kernel — bvh_amd/csrc/radius_body.inc (over point_walk.inc,
+// which has the distance functions) with the device helpers of bvh_amd/csrc/trace_device.h — for the HOST and runs it with
 // one emulated lane per query (the queries of a batch one after another, or split over host threads). What it can show: the walk of
 // the very source the device runs lists the primitives a brute force over the same distance functions lists, in the tree's order, and
 // keeps to its segment; the device's counts, lists and distances must equal these bit for bit. What it cannot show: anything that
 // needs the hardware. tests/test_radius_search_host.py drives it; tests/test_gpu_radius_search.py uses it too.
 //
 // Built by the tests with: g++ -std=c++20 -O1 -mavx2 -mfma -ffp-contract=off -fno-strict-aliasing -shared -fPIC -pthread.
-#include <algorithm>
-#include <cmath>
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#include "../../include/bvh_amd.h"                               // bvh_hit3f / bvh_hit3d, bvh_amd_counters, BVH_AMD_INVALID
-
-// ---- single-lane stand-ins for what hip_runtime.h provides ------------------------------------------------------------
-#define __device__
-#define __host__
-#define __global__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-
-struct float2 { float x, y; };
-struct float4 { float x, y, z, w; };
-struct double2 { double x, y; };
-struct uint2 { uint32_t x, y; };
-struct uint4 { uint32_t x, y, z, w; };
-inline float4 make_float4(float x, float y, float z, float w) { return {x, y, z, w}; }
-inline double2 make_double2(double x, double y) { return {x, y}; }
-inline uint32_t __float_as_uint(float x) { return __builtin_bit_cast(uint32_t, x); }
-inline float __uint_as_float(uint32_t x) { return __builtin_bit_cast(float, x); }
-inline long long __double_as_longlong(double x) { return __builtin_bit_cast(long long, x); }
-inline double __longlong_as_double(long long x) { return __builtin_bit_cast(double, x); }
-using std::min;
-
-// ---- stand-ins for bvh_amd/csrc/common.h (which needs the HIP headers) ------------------------------------------------------
-namespace bvh_amd {
-constexpr unsigned kCountBits = 4;
-constexpr uint32_t kCountMask = 15u;
-constexpr int kWave = 64;
-template <typename T> struct PairNode;
-template <> struct PairNode<float> { float lb[6], rb[6]; uint32_t li, ri; uint32_t pad[2]; };
-template <> struct PairNode<double> { double lb[6], rb[6]; uint32_t li, ri; uint32_t pad[6]; };
-template <typename T> struct HitOf;
-template <> struct HitOf<float> { using Type = bvh_hit3f; };
-template <> struct HitOf<double> { using Type = bvh_hit3d; };
-enum { LEAF_TRIANGLE = 0, LEAF_SPHERE = 1 };
-} // namespace bvh_amd
-
-#include "../../bvh_amd/csrc/trace_device.h"
+#include "host_lane_prelude.h"
 #include "../../bvh_amd/csrc/radius_body.inc"
 
 namespace {

@@ -1,4 +1,4 @@
-"""CPU: the TEXT of the closest-point kernel (bvh_amd/csrc/closest_body.inc + trace_device.h) compiled for the host by
+"""CPU: the TEXT of the closest-point kernel (bvh_amd/csrc/closest_body.inc + point_walk.inc + trace_device.h) compiled for the host by
 tests/cpp/closest_body_host.cpp. The per-primitive distance functions, float and double, against a float64 closest point on crafted
 cases (the seven Voronoi regions of a triangle, points on it, degenerate triangles, vertices collinear up to rounding, spheres); the
 walk over the golden trees against a brute force over the same function. The device's records must equal this harness's bit for bit (tests/test_gpu_closest_point.py)."""
@@ -321,3 +321,17 @@ def test_deep_chain(dll, orc, depth):
     brute_d2, bi = host_brute(dll, prims, q, 0)
     assert (hits["prim"] == bi).all() and (hits["prim"] == depth).all()
     assert (hits["t"] == np.sqrt(brute_d2)).all()
+
+
+def test_deep_chain_fills_the_spill(dll, orc):
+    """70 levels, one push per level: the stack crosses LDS -> scratch (entry 8), scratch -> HBM (entry 64) and ends on the last of
+    the 6 HBM entries it is given."""
+    depth = 70
+    tris, nodes, ids = chain_tree(depth, orc.prep_tris)
+    prims = precompute(tris, np.float32)
+    q = chain_queries(depth, 48)
+    hits, cnt = host_walk(dll, nodes["bounds"], nodes["index"], prims, q, 0, deep_cap=depth - 64)
+    brute_d2, bi = host_brute(dll, prims, q, 0)
+    assert (hits["prim"] == bi).all() and (hits["prim"] == depth).all()
+    assert (hits["t"] == np.sqrt(brute_d2)).all()
+    assert cnt[0] == depth * len(q)                          # every level's record fetched once: nothing popped was walked again

@@ -1,4 +1,4 @@
-"""CPU: the TEXT of the k-nearest kernel (bvh_amd/csrc/knn_body.inc + closest_body.inc + trace_device.h) compiled for the host by
+"""CPU: the TEXT of the k-nearest kernel (bvh_amd/csrc/knn_body.inc + point_walk.inc + trace_device.h) compiled for the host by
 tests/cpp/knn_body_host.cpp. The walk over the golden trees against the k smallest (d2, index) pairs of a brute force over the same
 distance functions; k = 1 against the closest-point harness, byte for byte; short rows against the radius harness's lists; edge
 queries, padding and guard zones; trees deeper than 64 levels; the lane stride of the LDS arrays; the exported symbols. The device's
@@ -252,6 +252,19 @@ def test_deep_chain(dll, orc, depth):
     ids, dist, counts, _ = host_knn(dll, tree, q, 5, deep_cap=depth - 63)
     assert (counts == 5).all() and (ids == np.arange(depth, depth - 5, -1, dtype=np.uint32)).all()
     assert (np.diff(dist, axis=1) > 0).all()
+
+
+def test_deep_chain_fills_the_spill(dll, radius_dll, orc):
+    """70 levels, one push per level: the stack crosses LDS -> scratch (entry 8), scratch -> HBM (entry 64) and ends on the last of
+    the 6 HBM entries it is given; the rows are made of the entries popped from there."""
+    depth = 70
+    tris, nodes, _ = chain_tree(depth, orc.prep_tris)
+    tree = Tree(nodes["bounds"], nodes["index"], precompute(tris, np.float32), 0)
+    q = chain_queries(depth, 48)
+    ids, dist, counts, _ = host_knn(dll, tree, q, 8, deep_cap=depth - 64)
+    eids, ed2, _ = expected_rows(brute_order(host_brute(radius_dll, tree, q), np.float32(np.inf)), 8)
+    assert (counts == 8).all() and (ids == eids).all() and (ids == np.arange(depth, depth - 8, -1)).all()
+    assert (dist == np.sqrt(ed2)).all()
 
 
 def test_stride_independence(dll, orc):

@@ -1,4 +1,4 @@
-"""CPU: the TEXT of the radius-query kernel (bvh_amd/csrc/radius_body.inc + closest_body.inc + trace_device.h) compiled for the host by
+"""CPU: the TEXT of the radius-query kernel (bvh_amd/csrc/radius_body.inc + point_walk.inc + trace_device.h) compiled for the host by
 tests/cpp/radius_body_host.cpp. The walk over the golden trees against a brute force over the same distance functions, filtered in
 the tree's left-first depth-first order; the shapes of the output (count pass, exact offsets, fixed segments, padding, guard zones);
 edge queries; trees deeper than 64 levels; the exported symbols. The device's counts, lists and distances must equal this harness's
@@ -268,6 +268,22 @@ def test_deep_chain(dll, orc, depth):
     assert (counts == within.sum(axis=1)).all() and 0 < counts.min() and counts.max() < 20
     for k in range(len(q)):
         assert (ids[int(offsets[k]):int(offsets[k + 1])] == np.flatnonzero(within[k])).all()
+
+
+def test_deep_chain_fills_the_spill(dll, orc):
+    """The chain with every inner child on the left, so that this left-first walk stacks one leaf per level: 70 levels cross LDS ->
+    scratch (entry 16), scratch -> HBM (entry 64) and end on the last of the 6 HBM entries given."""
+    depth = 70
+    tris, nodes, _ = chain_tree(depth, orc.prep_tris)
+    nodes[1::2], nodes[2::2] = nodes[2::2].copy(), nodes[1::2].copy()
+    tree = Tree(nodes["bounds"], nodes["index"], precompute(tris, np.float32), 0)
+    q = chain_queries(depth, 48)
+    dfs = dfs_prim_order(nodes["index"])
+    assert (dfs == np.arange(depth, -1, -1)).all()
+    offsets, ids, dist, counts, _ = host_radius(dll, tree, q, deep_cap=depth - 64)
+    d2 = host_brute(dll, tree, q)
+    assert (counts == depth + 1).all() and (ids.reshape(len(q), depth + 1) == dfs).all()
+    assert (dist.reshape(len(q), depth + 1) == np.sqrt(d2)[:, dfs]).all()
 
 
 def test_radius_symbols_are_declared_and_exported():
