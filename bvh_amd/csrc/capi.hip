@@ -4,6 +4,7 @@
 
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 namespace bvh_amd {
 
@@ -33,13 +34,50 @@ namespace {
 
 struct ThreadPoolTag { size_t thread_count; };   // opaque `bvh_thread_pool`: only its presence matters
 
-template <typename T> struct CTypes;
-template <> struct CTypes<float>  { using Bvh = bvh3f; using Node = bvh_node3f; using BBox = bvh_bbox3f; using Vec = bvh_vec3f; using Ray = bvh_ray3f; };
-template <> struct CTypes<double> { using Bvh = bvh3d; using Node = bvh_node3d; using BBox = bvh_bbox3d; using Vec = bvh_vec3d; using Ray = bvh_ray3d; };
+// ---- the four families of the reference's C API (c_api/bvh.cpp:7-10): scalar T, dimension D. All of them are the same BvhImpl<T>:
+// a 2D one has dim = 2, its inputs are widened to z = 0 on the device, and the host mirror its caller sees is BvhImpl::nodes2 in the
+// reference's 20/40-byte layout. Everything below that depends on the family asks this trait.
+template <typename T, int D> struct CTypes;
+template <> struct CTypes<float, 3>  { using Bvh = bvh3f; using Node = bvh_node3f; using BBox = bvh_bbox3f; using Vec = bvh_vec3f; using Ray = bvh_ray3f; };
+template <> struct CTypes<double, 3> { using Bvh = bvh3d; using Node = bvh_node3d; using BBox = bvh_bbox3d; using Vec = bvh_vec3d; using Ray = bvh_ray3d; };
+template <> struct CTypes<float, 2>  { using Bvh = bvh2f; using Node = bvh_node2f; using BBox = bvh_bbox2f; using Vec = bvh_vec2f; using Ray = bvh_ray2f; };
+template <> struct CTypes<double, 2> { using Bvh = bvh2d; using Node = bvh_node2d; using BBox = bvh_bbox2d; using Vec = bvh_vec2d; using Ray = bvh_ray2d; };
 
-template <typename T> BvhImpl<T>* impl(typename CTypes<T>::Bvh* b) { return reinterpret_cast<BvhImpl<T>*>(b); }
-template <typename T> const BvhImpl<T>* impl(const typename CTypes<T>::Bvh* b) { return reinterpret_cast<const BvhImpl<T>*>(b); }
-template <typename T> typename CTypes<T>::Bvh* handle(BvhImpl<T>* b) { return reinterpret_cast<typename CTypes<T>::Bvh*>(b); }
+template <typename T, int D>
+struct Family : CTypes<T, D> {
+    using MirrorNode = std::conditional_t<D == 3, HostNode<T>, HostNode2<T>>;     // what `Node*` points at
+    static constexpr int kBox = 2 * D, kVec = D, kRay = 2 * D + 2;                 // components of a BBox / Vec / Ray
+    static_assert(sizeof(typename CTypes<T, D>::BBox) == kBox * sizeof(T) && sizeof(typename CTypes<T, D>::Vec) == kVec * sizeof(T) &&
+                  sizeof(typename CTypes<T, D>::Ray) == kRay * sizeof(T));
+    static constexpr int kRefitBoxes = D == 3 ? REFIT_BOXES3 : REFIT_BOXES2;
+    static std::vector<MirrorNode>& mirror(const BvhImpl<T>& b) { if constexpr (D == 3) return b.nodes; else return b.nodes2; }
+    static int sync_mirror(const BvhImpl<T>& b) { if constexpr (D == 3) return b.sync_host(); else return b.sync_host2(); }
+    static int sphere_bounds(const T* d_prims, size_t n, T* d_bb, T* d_cc, hipStream_t s) {      // spheres {c, r} / circles {c, r}
+        if constexpr (D == 3) return launch_sphere_bounds<T>(d_prims, n, d_bb, d_cc, s); else return launch_circle_bounds<T>(d_prims, n, d_bb, d_cc, s);
+    }
+};
+
+template <typename T, int D> BvhImpl<T>* impl(typename Family<T, D>::Bvh* b) { return reinterpret_cast<BvhImpl<T>*>(b); }
+template <typename T, int D> const BvhImpl<T>* impl(const typename Family<T, D>::Bvh* b) { return reinterpret_cast<const BvhImpl<T>*>(b); }
+template <typename T, int D> typename Family<T, D>::Bvh* handle(BvhImpl<T>* b) { return reinterpret_cast<typename Family<T, D>::Bvh*>(b); }
+
+// `who` works on a BVH of the current device only (`required` = false: an empty batch may name any BVH).
+template <typename T>
+int on_current_device(const BvhImpl<T>& b, const char* who, bool required = true) {
+    int cur = -1;
+    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
+    if (required && cur != b.device) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH lives on another device than the current one");
+    return BVH_AMD_OK;
+}
+
+// Two temporary device buffers of one call, freed on every path out of it (after whatever the call waits for first).
+template <typename T>
+struct DeviceTemps {
+    T *first = nullptr, *second = nullptr;
+    DeviceTemps() = default;
+    DeviceTemps(const DeviceTemps&) = delete;
+    ~DeviceTemps() { if (first) (void)hipFree(first); if (second) (void)hipFree(second); }
+};
 
 bvh_build_config default_config() {               // default_builder.h:23-30, top_down_sah_builder.h:27-40
     bvh_build_config c;
@@ -73,9 +111,10 @@ auto with_bins(const bvh_amd_sah_config* sah, size_t bin_count, Build&& build) -
     return with_sah(sah, [&] { ambient_sah().bin_count = static_cast<uint32_t>(bin_count); return build(); });
 }
 
-template <typename T>
-typename CTypes<T>::Bvh* build_device(const T* d_bboxes, const T* d_centers, size_t n, const bvh_build_config* config,
-                                      bvh_amd_builder builder, void* stream)
+// `d_bboxes` / `d_centers` hold 2 * D / D components per primitive; the builders work on 6 / 3 (2D: widened into temporaries first).
+template <typename T, int D>
+typename Family<T, D>::Bvh* build_device(const T* d_bboxes, const T* d_centers, size_t n, const bvh_build_config* config,
+                                         bvh_amd_builder builder, void* stream_)
 {
     if (!d_bboxes || !d_centers || n == 0) { set_error("build: empty input (the reference's behaviour is undefined for 0 primitives)"); return nullptr; }
     bvh_build_config cfg = config ? *config : default_config();
@@ -83,14 +122,27 @@ typename CTypes<T>::Bvh* build_device(const T* d_bboxes, const T* d_centers, siz
         set_error("build: need 1 <= min_leaf_size <= max_leaf_size <= 15 (4-bit primitive count, index.h:38)");
         return nullptr;
     }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
     auto b = std::make_unique<BvhImpl<T>>();
-    if (build_on_device<T>(*b, d_bboxes, d_centers, n, cfg, builder, static_cast<hipStream_t>(stream)) != BVH_AMD_OK)
-        return nullptr;
-    return handle<T>(b.release());
+    b->dim = D;
+    int rc;
+    if constexpr (D == 3) {
+        rc = build_on_device<T>(*b, d_bboxes, d_centers, n, cfg, builder, stream);
+    } else {
+        DeviceTemps<T> tmp;
+        auto& [d_bb6, d_cc3] = tmp;
+        BVH_HIP_TRY_PTR(hipMalloc(&d_bb6, n * 6 * sizeof(T)));
+        hipError_t e = hipMalloc(&d_cc3, n * 3 * sizeof(T));
+        rc = e == hipSuccess ? launch_widen_inputs<T>(d_bboxes, d_centers, n, d_bb6, d_cc3, stream)
+                             : fail(BVH_AMD_ERR_HIP, std::string("build: ") + hipGetErrorString(e));
+        if (rc == BVH_AMD_OK) rc = build_on_device<T>(*b, d_bb6, d_cc3, n, cfg, builder, stream);
+        (void)hipStreamSynchronize(stream);
+    }
+    return rc == BVH_AMD_OK ? handle<T, D>(b.release()) : nullptr;
 }
 
 template <typename T>
-typename CTypes<T>::Bvh* build_minitree(const T* d_bboxes, const T* d_centers, size_t n, const bvh_amd_minitree_config* config, void* stream) {
+typename Family<T, 3>::Bvh* build_minitree(const T* d_bboxes, const T* d_centers, size_t n, const bvh_amd_minitree_config* config, void* stream) {
     if (!d_bboxes || !d_centers || n == 0) { set_error("build: empty input"); return nullptr; }
     bvh_amd_minitree_config c = config ? *config : bvh_amd_minitree_config{1, 8, 1, 0.01, 1024, 4, 0, 1.0};
     if (c.min_leaf_size < 1 || c.min_leaf_size > c.max_leaf_size || c.max_leaf_size > 15) {
@@ -111,101 +163,114 @@ typename CTypes<T>::Bvh* build_minitree(const T* d_bboxes, const T* d_centers, s
     if (build_minitree_explicit<T>(*b, d_bboxes, d_centers, n, cfg, c.enable_pruning != 0, static_cast<T>(c.pruning_area_ratio), false,
                                    static_cast<uint32_t>(c.log2_grid_dim), static_cast<hipStream_t>(stream)) != BVH_AMD_OK)
         return nullptr;
-    return handle<T>(b.release());
+    return handle<T, 3>(b.release());
 }
 
-template <typename T>
-typename CTypes<T>::Bvh* build_host(bvh_thread_pool* pool, const typename CTypes<T>::BBox* bboxes,
-                                    const typename CTypes<T>::Vec* centers, size_t n, const bvh_build_config* config)
+template <typename T, int D>
+typename Family<T, D>::Bvh* build_host(bvh_thread_pool* pool, const typename Family<T, D>::BBox* bboxes,
+                                       const typename Family<T, D>::Vec* centers, size_t n, const bvh_build_config* config)
 {
+    using F = Family<T, D>;
     if (!bboxes || !centers || n == 0) { set_error("build: empty input"); return nullptr; }
-    static_assert(sizeof(typename CTypes<T>::BBox) == 6 * sizeof(T) && sizeof(typename CTypes<T>::Vec) == 3 * sizeof(T));
-    T *d_bb = nullptr, *d_cc = nullptr;
-    BVH_HIP_TRY_PTR(hipMalloc(&d_bb, n * 6 * sizeof(T)));
-    hipError_t e = hipMalloc(&d_cc, n * 3 * sizeof(T));
-    if (e == hipSuccess) e = hipMemcpy(d_bb, bboxes, n * 6 * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_cc, centers, n * 3 * sizeof(T), hipMemcpyHostToDevice);
-    typename CTypes<T>::Bvh* out = nullptr;
+    DeviceTemps<T> tmp;
+    auto& [d_bb, d_cc] = tmp;
+    BVH_HIP_TRY_PTR(hipMalloc(&d_bb, n * F::kBox * sizeof(T)));
+    hipError_t e = hipMalloc(&d_cc, n * F::kVec * sizeof(T));
+    if (e == hipSuccess) e = hipMemcpy(d_bb, bboxes, n * F::kBox * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_cc, centers, n * F::kVec * sizeof(T), hipMemcpyHostToDevice);
+    typename F::Bvh* out = nullptr;
     if (e == hipSuccess)
-        out = build_device<T>(d_bb, d_cc, n, config, pool ? BVH_AMD_BUILDER_DEFAULT_PARALLEL : BVH_AMD_BUILDER_DEFAULT_SERIAL, nullptr);
+        out = build_device<T, D>(d_bb, d_cc, n, config, pool ? BVH_AMD_BUILDER_DEFAULT_PARALLEL : BVH_AMD_BUILDER_DEFAULT_SERIAL, nullptr);
     else
         set_error(std::string("build: ") + hipGetErrorString(e));
     (void)hipDeviceSynchronize();
-    (void)hipFree(d_bb);
-    if (d_cc) (void)hipFree(d_cc);
     return out;
 }
 
-template <typename T>
-typename CTypes<T>::Bvh* from_nodes(const void* nodes, size_t nn, const size_t* prim_ids, size_t np) {
+// A BVH around the mirror of `b`, filled in the family's layout by the caller (from_nodes / deserialize): uploaded, and handed out.
+template <typename T, int D>
+typename Family<T, D>::Bvh* adopt_mirror(std::unique_ptr<BvhImpl<T>> b) {
+    b->dim = D;
+    if constexpr (D == 2) b->widen_host();
+    if (upload_bvh<T>(*b, nullptr) != BVH_AMD_OK) return nullptr;
+    if constexpr (D == 2) b->nodes2_valid = true;
+    return handle<T, D>(b.release());
+}
+
+template <typename T, int D>
+typename Family<T, D>::Bvh* from_nodes(const void* nodes, size_t nn, const size_t* prim_ids, size_t np) {
+    using F = Family<T, D>;
     if (!nodes || nn == 0 || (!prim_ids && np)) { set_error("from_nodes: null/empty input"); return nullptr; }
     auto b = std::make_unique<BvhImpl<T>>();
-    b->nodes.resize(nn);
-    std::memcpy(b->nodes.data(), nodes, nn * sizeof(HostNode<T>));
+    F::mirror(*b).resize(nn);
+    std::memcpy(F::mirror(*b).data(), nodes, nn * sizeof(typename F::MirrorNode));
     b->prim_ids.assign(prim_ids, prim_ids + np);
-    if (upload_bvh<T>(*b, nullptr) != BVH_AMD_OK) return nullptr;
-    return handle<T>(b.release());
+    return adopt_mirror<T, D>(std::move(b));
 }
 
-// Byte stream of Bvh::serialize (bvh.h:221-229): [node_count][prim_count] in Index::Type, nodes, prim ids.
-template <typename T>
+// Byte stream of Bvh::serialize (bvh.h:221-229): [node_count][prim_count] in Index::Type, Node<T, D> records, prim ids.
+template <typename T, int D>
 size_t stream_size(const BvhImpl<T>& b) {
     using I = typename IndexOf<T>::Type;
-    return 2 * sizeof(I) + b.node_count * sizeof(HostNode<T>) + b.prim_count * sizeof(I);
+    return 2 * sizeof(I) + b.node_count * sizeof(typename Family<T, D>::MirrorNode) + b.prim_count * sizeof(I);
 }
 
-template <typename T>
+template <typename T, int D>
 size_t serialize(const BvhImpl<T>& b, void* out, size_t cap) {
+    using F = Family<T, D>;
     using I = typename IndexOf<T>::Type;
-    size_t need = stream_size(b);
+    const size_t need = stream_size<T, D>(b);
     if (!out || cap < need) return need;
-    if (b.sync_host() != BVH_AMD_OK) return 0;
+    if (F::sync_mirror(b) != BVH_AMD_OK) return 0;
+    const auto& nodes = F::mirror(b);
     auto p = static_cast<uint8_t*>(out);
-    I hdr[2] = { static_cast<I>(b.nodes.size()), static_cast<I>(b.prim_ids.size()) };
+    I hdr[2] = { static_cast<I>(nodes.size()), static_cast<I>(b.prim_ids.size()) };
     std::memcpy(p, hdr, sizeof(hdr)); p += sizeof(hdr);
-    std::memcpy(p, b.nodes.data(), b.nodes.size() * sizeof(HostNode<T>)); p += b.nodes.size() * sizeof(HostNode<T>);
+    std::memcpy(p, nodes.data(), nodes.size() * sizeof(nodes[0])); p += nodes.size() * sizeof(nodes[0]);
     for (size_t id : b.prim_ids) { I v = static_cast<I>(id); std::memcpy(p, &v, sizeof(v)); p += sizeof(v); }
     return need;
 }
 
-template <typename T>
-typename CTypes<T>::Bvh* deserialize(const void* bytes, size_t size) {
+template <typename T, int D>
+typename Family<T, D>::Bvh* deserialize(const void* bytes, size_t size) {
+    using F = Family<T, D>;
     using I = typename IndexOf<T>::Type;
+    constexpr size_t node_bytes = sizeof(typename F::MirrorNode);
     if (!bytes || size < 2 * sizeof(I)) { set_error("deserialize: truncated stream"); return nullptr; }
     auto p = static_cast<const uint8_t*>(bytes);
     I hdr[2];
     std::memcpy(hdr, p, sizeof(hdr)); p += sizeof(hdr);
-    size_t nn = hdr[0], np = hdr[1];
-    if (nn > size / sizeof(HostNode<T>) || np > size / sizeof(I) ||           // (bounded first: a crafted header must not overflow the sum)
-        size < 2 * sizeof(I) + nn * sizeof(HostNode<T>) + np * sizeof(I)) { set_error("deserialize: truncated stream"); return nullptr; }
+    const size_t nn = hdr[0], np = hdr[1];
+    if (nn > size / node_bytes || np > size / sizeof(I) ||                     // (bounded first: a crafted header must not overflow the sum)
+        size < 2 * sizeof(I) + nn * node_bytes + np * sizeof(I)) { set_error("deserialize: truncated stream"); return nullptr; }
     auto b = std::make_unique<BvhImpl<T>>();
-    b->nodes.resize(nn);
-    std::memcpy(b->nodes.data(), p, nn * sizeof(HostNode<T>)); p += nn * sizeof(HostNode<T>);
+    F::mirror(*b).resize(nn);
+    std::memcpy(F::mirror(*b).data(), p, nn * node_bytes); p += nn * node_bytes;
     b->prim_ids.resize(np);
     for (size_t i = 0; i < np; ++i) { I v; std::memcpy(&v, p, sizeof(v)); p += sizeof(v); b->prim_ids[i] = static_cast<size_t>(v); }
-    if (upload_bvh<T>(*b, nullptr) != BVH_AMD_OK) return nullptr;
-    return handle<T>(b.release());
+    return adopt_mirror<T, D>(std::move(b));
 }
 
-template <typename T>
+template <typename T, int D>
 void save(const BvhImpl<T>& b, FILE* f) {
-    std::vector<uint8_t> buf(stream_size(b));
-    serialize(b, buf.data(), buf.size());
+    std::vector<uint8_t> buf(stream_size<T, D>(b));
+    serialize<T, D>(b, buf.data(), buf.size());
     fwrite(buf.data(), 1, buf.size(), f);
 }
 
-template <typename T>
-typename CTypes<T>::Bvh* load(FILE* f) {
+template <typename T, int D>
+typename Family<T, D>::Bvh* load(FILE* f) {
     using I = typename IndexOf<T>::Type;
+    constexpr size_t node_bytes = sizeof(typename Family<T, D>::MirrorNode);
     I hdr[2] = {0, 0};
     if (fread(hdr, sizeof(I), 2, f) != 2) { set_error("load: truncated stream"); return nullptr; }
     std::vector<uint8_t> buf;
-    try { buf.resize(2 * sizeof(I) + size_t(hdr[0]) * sizeof(HostNode<T>) + size_t(hdr[1]) * sizeof(I)); }
+    try { buf.resize(2 * sizeof(I) + size_t(hdr[0]) * node_bytes + size_t(hdr[1]) * sizeof(I)); }
     catch (const std::exception&) { set_error("load: the header asks for more memory than there is"); return nullptr; }   // (never across the C ABI)
     std::memcpy(buf.data(), hdr, sizeof(hdr));
     size_t rest = buf.size() - sizeof(hdr);
     if (fread(buf.data() + sizeof(hdr), 1, rest, f) != rest) { set_error("load: truncated stream"); return nullptr; }
-    return deserialize<T>(buf.data(), buf.size());
+    return deserialize<T, D>(buf.data(), buf.size());
 }
 
 // The reference-layout nodes resident on the device, with possible host-side edits pushed.
@@ -321,9 +386,7 @@ int refit_prims(BvhImpl<T>* pb, int src_kind, const T* d_src, size_t n_src, T* d
     if (!d_src) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": null primitive array");
     BvhImpl<T>& b = *pb;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (cur != b.device) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH lives on another device than the current one");
+    if (const int rc = on_current_device(b, who)) return rc;
     if (b.node_count == 0 || !b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH has no device copy");
     if (b.max_prim_id < 0) {
         uint32_t largest = 0;
@@ -359,10 +422,15 @@ int refit_prims(BvhImpl<T>* pb, int src_kind, const T* d_src, size_t n_src, T* d
 template <typename T>
 int traversal_cost_checked(const BvhImpl<T>* b, double* cost_out, void* stream) {
     if (!b || !cost_out) return fail(BVH_AMD_ERR_ARG, "traversal_cost: null bvh or output");
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (cur != b->device) return fail(BVH_AMD_ERR_ARG, "traversal_cost: BVH lives on another device than the current one");
+    if (const int rc = on_current_device(*b, "traversal_cost")) return rc;
     return traversal_cost<T>(*b, cost_out, static_cast<hipStream_t>(stream));
+}
+
+template <typename T>
+int prepare_trace_checked(const BvhImpl<T>* b, size_t n_rays_hint, void* stream) {
+    if (!b) return fail(BVH_AMD_ERR_ARG, "prepare_trace: null bvh");
+    if (const int rc = on_current_device(*b, "prepare_trace")) return rc;
+    return prepare_trace<T>(*b, n_rays_hint, static_cast<hipStream_t>(stream));
 }
 
 // Host-side edits (bvh_node* setters, append/remove) live in the mirror; this pushes them to the device copy.
@@ -376,167 +444,93 @@ template <typename T> int sync_device(BvhImpl<T>* pb) {
     return upload_bvh<T>(b, nullptr);
 }
 
-// ---- the 2D families (c_api/bvh.cpp:7-10): the same BvhImpl with dim = 2; inputs are widened to z = 0 on the device, the
-// host mirror the caller sees is BvhImpl::nodes2 in the reference's 20/40-byte layout ------------------------------------------
-template <typename T> struct CTypes2;
-template <> struct CTypes2<float>  { using Bvh = bvh2f; using Node = bvh_node2f; using BBox = bvh_bbox2f; using Vec = bvh_vec2f; using Ray = bvh_ray2f; };
-template <> struct CTypes2<double> { using Bvh = bvh2d; using Node = bvh_node2d; using BBox = bvh_bbox2d; using Vec = bvh_vec2d; using Ray = bvh_ray2d; };
-template <typename T> BvhImpl<T>* impl2(typename CTypes2<T>::Bvh* b) { return reinterpret_cast<BvhImpl<T>*>(b); }
-template <typename T> const BvhImpl<T>* impl2(const typename CTypes2<T>::Bvh* b) { return reinterpret_cast<const BvhImpl<T>*>(b); }
-template <typename T> typename CTypes2<T>::Bvh* handle2(BvhImpl<T>* b) { return reinterpret_cast<typename CTypes2<T>::Bvh*>(b); }
+// ---- the host mirror through the family's `Node*` (c_api/bvh.h:170-218). A caller's edits reach the device with sync_device --------
+template <typename T, int D> auto* mirror_node(typename Family<T, D>::Node* n) { return reinterpret_cast<typename Family<T, D>::MirrorNode*>(n); }
+template <typename T, int D> auto* mirror_node(const typename Family<T, D>::Node* n) { return reinterpret_cast<const typename Family<T, D>::MirrorNode*>(n); }
 
-template <typename T>
-typename CTypes2<T>::Bvh* build2_device(const T* d_bb4, const T* d_cc2, size_t n, const bvh_build_config* config, bvh_amd_builder builder, void* stream) {
-    if (!d_bb4 || !d_cc2 || n == 0) { set_error("build: empty input (the reference's behaviour is undefined for 0 primitives)"); return nullptr; }
-    bvh_build_config cfg = config ? *config : default_config();
-    if (cfg.min_leaf_size < 1 || cfg.min_leaf_size > cfg.max_leaf_size || cfg.max_leaf_size > 15) {
-        set_error("build: need 1 <= min_leaf_size <= max_leaf_size <= 15 (4-bit primitive count, index.h:38)");
-        return nullptr;
-    }
-    T *d_bb6 = nullptr, *d_cc3 = nullptr;
-    BVH_HIP_TRY_PTR(hipMalloc(&d_bb6, n * 6 * sizeof(T)));
-    hipError_t e = hipMalloc(&d_cc3, n * 3 * sizeof(T));
-    auto b = std::make_unique<BvhImpl<T>>();
-    b->dim = 2;
-    int rc = e == hipSuccess ? launch_widen_inputs<T>(d_bb4, d_cc2, n, d_bb6, d_cc3, static_cast<hipStream_t>(stream))
-                             : fail(BVH_AMD_ERR_HIP, std::string("build: ") + hipGetErrorString(e));
-    if (rc == BVH_AMD_OK) rc = build_on_device<T>(*b, d_bb6, d_cc3, n, cfg, builder, static_cast<hipStream_t>(stream));
-    (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));
-    (void)hipFree(d_bb6);
-    if (d_cc3) (void)hipFree(d_cc3);
-    return rc == BVH_AMD_OK ? handle2<T>(b.release()) : nullptr;
-}
-
-template <typename T>
-typename CTypes2<T>::Bvh* build2_host(bvh_thread_pool* pool, const typename CTypes2<T>::BBox* bboxes, const typename CTypes2<T>::Vec* centers, size_t n,
-                                      const bvh_build_config* config) {
-    if (!bboxes || !centers || n == 0) { set_error("build: empty input"); return nullptr; }
-    static_assert(sizeof(typename CTypes2<T>::BBox) == 4 * sizeof(T) && sizeof(typename CTypes2<T>::Vec) == 2 * sizeof(T));
-    T *d_bb = nullptr, *d_cc = nullptr;
-    BVH_HIP_TRY_PTR(hipMalloc(&d_bb, n * 4 * sizeof(T)));
-    hipError_t e = hipMalloc(&d_cc, n * 2 * sizeof(T));
-    if (e == hipSuccess) e = hipMemcpy(d_bb, bboxes, n * 4 * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_cc, centers, n * 2 * sizeof(T), hipMemcpyHostToDevice);
-    typename CTypes2<T>::Bvh* out = nullptr;
-    if (e == hipSuccess)
-        out = build2_device<T>(d_bb, d_cc, n, config, pool ? BVH_AMD_BUILDER_DEFAULT_PARALLEL : BVH_AMD_BUILDER_DEFAULT_SERIAL, nullptr);
-    else
-        set_error(std::string("build: ") + hipGetErrorString(e));
-    (void)hipDeviceSynchronize();
-    (void)hipFree(d_bb);
-    if (d_cc) (void)hipFree(d_cc);
-    return out;
-}
-
-template <typename T>
-BvhImpl<T>* adopt_nodes2(const HostNode2<T>* nodes, size_t nn, std::vector<size_t>&& ids) {
-    auto b = std::make_unique<BvhImpl<T>>();
-    b->dim = 2;
-    b->nodes2.assign(nodes, nodes + nn);
-    b->widen_host();
-    b->prim_ids = std::move(ids);
-    if (upload_bvh<T>(*b, nullptr) != BVH_AMD_OK) return nullptr;
-    b->nodes2_valid = true;
-    return b.release();
-}
-
-template <typename T>
-typename CTypes2<T>::Bvh* from_nodes2(const void* nodes, size_t nn, const size_t* prim_ids, size_t np) {
-    if (!nodes || nn == 0 || (!prim_ids && np)) { set_error("from_nodes: null/empty input"); return nullptr; }
-    return handle2<T>(adopt_nodes2<T>(static_cast<const HostNode2<T>*>(nodes), nn, std::vector<size_t>(prim_ids, prim_ids + np)));
-}
-
-template <typename T>
-size_t stream_size2(const BvhImpl<T>& b) {
+template <typename T, int D> void set_prim_count(typename Family<T, D>::Node* n, size_t c) {
     using I = typename IndexOf<T>::Type;
-    return 2 * sizeof(I) + b.node_count * sizeof(HostNode2<T>) + b.prim_count * sizeof(I);
+    auto h = mirror_node<T, D>(n);
+    h->index = (h->index & ~static_cast<I>(kCountMask)) | (static_cast<I>(c) & kCountMask);
+}
+template <typename T, int D> void set_first_id(typename Family<T, D>::Node* n, size_t f) {
+    auto h = mirror_node<T, D>(n);
+    h->index = (static_cast<typename IndexOf<T>::Type>(f) << kCountBits) | (h->index & kCountMask);
+}
+template <typename T, int D> bool is_leaf(const typename Family<T, D>::Node* n) { return (mirror_node<T, D>(n)->index & kCountMask) != 0; }
+template <typename T, int D> size_t get_prim_count(const typename Family<T, D>::Node* n) { return mirror_node<T, D>(n)->index & kCountMask; }
+template <typename T, int D> size_t get_first_id(const typename Family<T, D>::Node* n) { return mirror_node<T, D>(n)->index >> kCountBits; }
+
+// A BBox is {min[D], max[D]}, a node's bounds are {min, max} per axis.
+template <typename T, int D> void set_bbox(typename Family<T, D>::Node* n, const typename Family<T, D>::BBox* bb) {
+    auto h = mirror_node<T, D>(n);
+    T v[2 * D];
+    std::memcpy(v, bb, sizeof(v));
+    for (int k = 0; k < D; ++k) { h->bounds[2 * k] = v[k]; h->bounds[2 * k + 1] = v[D + k]; }
+}
+template <typename T, int D> typename Family<T, D>::BBox get_bbox(const typename Family<T, D>::Node* n) {
+    auto h = mirror_node<T, D>(n);
+    T v[2 * D];
+    for (int k = 0; k < D; ++k) { v[k] = h->bounds[2 * k]; v[D + k] = h->bounds[2 * k + 1]; }
+    typename Family<T, D>::BBox r;
+    std::memcpy(&r, v, sizeof(r));
+    return r;
 }
 
-template <typename T>
-size_t serialize2(const BvhImpl<T>& b, void* out, size_t cap) {           // bvh.h:221-229 with Node<T, 2> records
-    using I = typename IndexOf<T>::Type;
-    const size_t need = stream_size2(b);
-    if (!out || cap < need) return need;
-    if (b.sync_host2() != BVH_AMD_OK) return 0;
-    auto p = static_cast<uint8_t*>(out);
-    I hdr[2] = { static_cast<I>(b.nodes2.size()), static_cast<I>(b.prim_ids.size()) };
-    std::memcpy(p, hdr, sizeof(hdr)); p += sizeof(hdr);
-    std::memcpy(p, b.nodes2.data(), b.nodes2.size() * sizeof(HostNode2<T>)); p += b.nodes2.size() * sizeof(HostNode2<T>);
-    for (size_t id : b.prim_ids) { I v = static_cast<I>(id); std::memcpy(p, &v, sizeof(v)); p += sizeof(v); }
-    return need;
+template <typename T, int D> typename Family<T, D>::Node* get_node(BvhImpl<T>* b, size_t i) {
+    if (Family<T, D>::sync_mirror(*b) != BVH_AMD_OK) return nullptr;
+    return reinterpret_cast<typename Family<T, D>::Node*>(&Family<T, D>::mirror(*b)[i]);
+}
+template <typename T, int D> void append_node(BvhImpl<T>* b) {
+    auto& nodes = Family<T, D>::mirror(*b);
+    if (Family<T, D>::sync_mirror(*b) != BVH_AMD_OK) return;
+    nodes.emplace_back();
+    b->node_count = nodes.size();
+}
+template <typename T, int D> void remove_last_node(BvhImpl<T>* b) {
+    auto& nodes = Family<T, D>::mirror(*b);
+    if (Family<T, D>::sync_mirror(*b) != BVH_AMD_OK || nodes.empty()) return;
+    nodes.pop_back();
+    b->node_count = nodes.size();
+}
+template <typename T, int D> void copy_nodes(const BvhImpl<T>* b, void* out) {
+    const auto& nodes = Family<T, D>::mirror(*b);
+    if (Family<T, D>::sync_mirror(*b) != BVH_AMD_OK) return;
+    std::memcpy(out, nodes.data(), nodes.size() * sizeof(nodes[0]));
+}
+// (the prim ids are filled by sync_host() in every family)
+template <typename T> size_t get_prim_id(const BvhImpl<T>* b, size_t i) {
+    if (b->sync_host() != BVH_AMD_OK) return BVH_INVALID_PRIM_ID;
+    return b->prim_ids[i];
+}
+template <typename T> void copy_prim_ids(const BvhImpl<T>* b, size_t* out) {
+    if (b->sync_host() != BVH_AMD_OK) return;
+    std::memcpy(out, b->prim_ids.data(), b->prim_ids.size() * sizeof(size_t));
 }
 
-template <typename T>
-typename CTypes2<T>::Bvh* deserialize2(const void* bytes, size_t size) {
-    using I = typename IndexOf<T>::Type;
-    if (!bytes || size < 2 * sizeof(I)) { set_error("deserialize: truncated stream"); return nullptr; }
-    auto p = static_cast<const uint8_t*>(bytes);
-    I hdr[2];
-    std::memcpy(hdr, p, sizeof(hdr)); p += sizeof(hdr);
-    const size_t nn = hdr[0], np = hdr[1];
-    if (size < 2 * sizeof(I) + nn * sizeof(HostNode2<T>) + np * sizeof(I)) { set_error("deserialize: truncated stream"); return nullptr; }
-    std::vector<HostNode2<T>> nodes(nn);
-    std::memcpy(nodes.data(), p, nn * sizeof(HostNode2<T>)); p += nn * sizeof(HostNode2<T>);
-    std::vector<size_t> ids(np);
-    for (size_t i = 0; i < np; ++i) { I v; std::memcpy(&v, p, sizeof(v)); p += sizeof(v); ids[i] = static_cast<size_t>(v); }
-    return handle2<T>(adopt_nodes2<T>(nodes.data(), nn, std::move(ids)));
-}
-
-template <typename T>
-typename CTypes2<T>::Bvh* load2(FILE* f) {
-    using I = typename IndexOf<T>::Type;
-    I hdr[2] = {0, 0};
-    if (fread(hdr, sizeof(I), 2, f) != 2) { set_error("load: truncated stream"); return nullptr; }
-    std::vector<uint8_t> buf;
-    try { buf.resize(2 * sizeof(I) + size_t(hdr[0]) * sizeof(HostNode2<T>) + size_t(hdr[1]) * sizeof(I)); }
-    catch (const std::exception&) { set_error("load: the header asks for more memory than there is"); return nullptr; }
-    std::memcpy(buf.data(), hdr, sizeof(hdr));
-    const size_t rest = buf.size() - sizeof(hdr);
-    if (fread(buf.data() + sizeof(hdr), 1, rest, f) != rest) { set_error("load: truncated stream"); return nullptr; }
-    return deserialize2<T>(buf.data(), buf.size());
-}
-
-template <typename T>
-int intersect2(const typename CTypes2<T>::Bvh* bvh, const T* d_circles3, const typename CTypes2<T>::Ray* d_rays, size_t n, unsigned flags,
-               typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, void* stream) {
-    if (!bvh) return fail(BVH_AMD_ERR_ARG, "intersect_rays: null bvh");
-    static_assert(sizeof(typename CTypes2<T>::Ray) == 6 * sizeof(T));
-    const BvhImpl<T>& b = *impl2<T>(bvh);
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (cur != b.device) return fail(BVH_AMD_ERR_ARG, "intersect_rays: BVH lives on another device than the current one");
-    return launch_traverse<T>(b, LEAF_SPHERE, d_circles3, reinterpret_cast<const T*>(d_rays), n, flags, d_hits, d_counters,
-                              static_cast<hipStream_t>(stream));
-}
-
-template <typename T>
-int intersect(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const typename CTypes<T>::Ray* d_rays, size_t n,
+// bvhXX_intersect_rays_*: a batch of the family's rays (2 * D + 2 components each) through the tree; 2D has circles only (LEAF_SPHERE).
+template <typename T, int D>
+int intersect(const typename Family<T, D>::Bvh* bvh, int leaf, const T* d_prims, const typename Family<T, D>::Ray* d_rays, size_t n,
               unsigned flags, typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, void* stream)
 {
     if (!bvh) return fail(BVH_AMD_ERR_ARG, "intersect_rays: null bvh");
-    static_assert(sizeof(typename CTypes<T>::Ray) == 8 * sizeof(T));
-    const BvhImpl<T>& b = *impl<T>(bvh);
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (cur != b.device) return fail(BVH_AMD_ERR_ARG, "intersect_rays: BVH lives on another device than the current one");
+    const BvhImpl<T>& b = *impl<T, D>(bvh);
+    if (const int rc = on_current_device(b, "intersect_rays")) return rc;
     return launch_traverse<T>(b, leaf, d_prims, reinterpret_cast<const T*>(d_rays), n, flags, d_hits, d_counters,
                               static_cast<hipStream_t>(stream));
 }
 
 // The tree behind a point query `who` (closest_points, radius_search, knn): it must live on the current device, unless the batch is empty.
 template <typename T>
-int point_query_tree(const typename CTypes<T>::Bvh* bvh, size_t n, const char* who, const BvhImpl<T>** b)
+int point_query_tree(const typename Family<T, 3>::Bvh* bvh, size_t n, const char* who, const BvhImpl<T>** b)
 {
     if (!bvh) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": null bvh");
-    *b = impl<T>(bvh);
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (n != 0 && cur != (*b)->device) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH lives on another device than the current one");
-    return BVH_AMD_OK;
+    *b = impl<T, 3>(bvh);
+    return on_current_device(**b, who, n != 0);
 }
 
 template <typename T>
-int closest(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned flags,
+int closest(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned flags,
             typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, void* stream)
 {
     const BvhImpl<T>* b = nullptr;
@@ -545,7 +539,7 @@ int closest(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, cons
 }
 
 template <typename T>
-int radius_search(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned flags, uint32_t* d_counts,
+int radius_search(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned flags, uint32_t* d_counts,
                   const uint64_t* d_offsets, uint32_t* d_list_prims, T* d_list_dist, bvh_amd_counters* d_counters, void* stream)
 {
     const BvhImpl<T>* b = nullptr;
@@ -555,7 +549,7 @@ int radius_search(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims
 }
 
 template <typename T>
-int knn(const typename CTypes<T>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned k, unsigned flags, uint32_t* d_out_prims,
+int knn(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const T* d_queries4, size_t n, unsigned k, unsigned flags, uint32_t* d_out_prims,
         T* d_out_dist, uint32_t* d_counts, bvh_amd_counters* d_counters, void* stream)
 {
     const BvhImpl<T>* b = nullptr;
@@ -570,9 +564,7 @@ int intersect_ray_visit(const BvhImpl<T>* b, const void* ray, size_t start, unsi
                         void (*inner_fn)(void*, size_t), void* user) {
     if (!b || !ray) return fail(BVH_AMD_ERR_ARG, "intersect_ray: null bvh or ray");
     if (b->dim != D) return fail(BVH_AMD_ERR_ARG, "intersect_ray: dimension mismatch");
-    int cur = -1;
-    BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);
-    if (cur != b->device) return fail(BVH_AMD_ERR_ARG, "intersect_ray: BVH lives on another device than the current one");
+    if (const int rc = on_current_device(*b, "intersect_ray")) return rc;
     if (start == BVH_AMD_START_AT_ROOT) start = b->root_index;
     const T* r = static_cast<const T*>(ray);
     T ray8[8];
@@ -691,94 +683,77 @@ bvh_thread_pool* bvh_thread_pool_create(size_t thread_count) {
 }
 void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<ThreadPoolTag*>(p); }
 
-#define BVH_AMD_IMPL(T, S)                                                                                          \
+// What every family exports: forwarders only, the bodies are the templates above.
+#define BVH_AMD_IMPL(T, D, S)                                                                                       \
     bvh##S* bvh##S##_build(bvh_thread_pool* pool, const bvh_bbox##S* bb, const bvh_vec##S* cc, size_t n,            \
-                           const bvh_build_config* cfg) { return loud(build_host<T>(pool, bb, cc, n, cfg), "bvh" #S "_build"); } \
+                           const bvh_build_config* cfg) { return loud(build_host<T, D>(pool, bb, cc, n, cfg), "bvh" #S "_build"); } \
     bvh##S* bvh##S##_build_device(const T* d_bb, const T* d_cc, size_t n, const bvh_build_config* cfg,              \
                                   enum bvh_amd_builder builder, void* stream) {                                     \
-        return build_device<T>(d_bb, d_cc, n, cfg, builder, stream); }                                              \
+        return build_device<T, D>(d_bb, d_cc, n, cfg, builder, stream); }                                           \
     bvh##S* bvh##S##_build_sah(bvh_thread_pool* pool, const bvh_bbox##S* bb, const bvh_vec##S* cc, size_t n,        \
                                const bvh_build_config* cfg, const bvh_amd_sah_config* sah) {                       \
-        return with_sah(sah, [&] { return build_host<T>(pool, bb, cc, n, cfg); }); }                                \
+        return with_sah(sah, [&] { return build_host<T, D>(pool, bb, cc, n, cfg); }); }                             \
     bvh##S* bvh##S##_build_device_sah(const T* d_bb, const T* d_cc, size_t n, const bvh_build_config* cfg,          \
                                       enum bvh_amd_builder builder, const bvh_amd_sah_config* sah, void* stream) {  \
-        return with_sah(sah, [&] { return build_device<T>(d_bb, d_cc, n, cfg, builder, stream); }); }               \
+        return with_sah(sah, [&] { return build_device<T, D>(d_bb, d_cc, n, cfg, builder, stream); }); }            \
     bvh##S* bvh##S##_build_device_binned(const T* d_bb, const T* d_cc, size_t n, const bvh_build_config* cfg,       \
                                          const bvh_amd_sah_config* sah, size_t bin_count, void* stream) {           \
-        return with_bins(sah, bin_count, [&] { return build_device<T>(d_bb, d_cc, n, cfg, BVH_AMD_BUILDER_BINNED, stream); }); } \
+        return with_bins(sah, bin_count, [&] { return build_device<T, D>(d_bb, d_cc, n, cfg, BVH_AMD_BUILDER_BINNED, stream); }); } \
+    bvh##S* bvh##S##_extract(bvh##S* b, size_t root_id) { return handle<T, D>(extract<T>(impl<T, D>(b), root_id)); } \
+    bvh##S* bvh##S##_from_nodes(const void* nodes, size_t nn, const size_t* ids, size_t np) {                       \
+        return from_nodes<T, D>(nodes, nn, ids, np); }                                                              \
+    void bvh##S##_destroy(bvh##S* b) { delete impl<T, D>(b); }                                                      \
+    void bvh##S##_optimize(bvh_thread_pool*, bvh##S* b) { loud_or_abort(optimize<T>(impl<T, D>(b)), "bvh" #S "_optimize"); } \
+    int bvh##S##_optimize_config(bvh##S* b, const bvh_amd_optimize_config* c) { return optimize_config<T>(impl<T, D>(b), c); } \
+    void bvh##S##_refit(bvh##S* b) { loud_or_abort(refit<T>(impl<T, D>(b)), "bvh" #S "_refit"); }                  \
+    int bvh##S##_refit_status(bvh##S* b) { return refit<T>(impl<T, D>(b)); }                                        \
+    int bvh##S##_sync_device(bvh##S* b) { return sync_device<T>(impl<T, D>(b)); }                                    \
+    int bvh##S##_refit_boxes(bvh##S* b, const T* d_bb, size_t n, void* s) {                                         \
+        return refit_prims<T>(impl<T, D>(b), Family<T, D>::kRefitBoxes, d_bb, n, nullptr, s, "refit_boxes"); }       \
+    void bvh##S##_append_node(bvh##S* b) { append_node<T, D>(impl<T, D>(b)); }                                      \
+    void bvh##S##_remove_last_node(bvh##S* b) { remove_last_node<T, D>(impl<T, D>(b)); }                            \
+    void bvh_node##S##_set_prim_count(bvh_node##S* n, size_t c) { set_prim_count<T, D>(n, c); }                     \
+    void bvh_node##S##_set_first_id(bvh_node##S* n, size_t f) { set_first_id<T, D>(n, f); }                         \
+    void bvh_node##S##_set_bbox(bvh_node##S* n, const bvh_bbox##S* bb) { set_bbox<T, D>(n, bb); }                   \
+    void bvh##S##_save(const bvh##S* b, FILE* f) { if (b && f) save<T, D>(*impl<T, D>(b), f); }                     \
+    bvh##S* bvh##S##_load(FILE* f) { return f ? load<T, D>(f) : nullptr; }                                          \
+    size_t bvh##S##_serialize(const bvh##S* b, void* out, size_t cap) { return b ? serialize<T, D>(*impl<T, D>(b), out, cap) : 0; } \
+    bvh##S* bvh##S##_deserialize(const void* bytes, size_t size) { return deserialize<T, D>(bytes, size); }         \
+    size_t bvh##S##_serialize_device(bvh##S* b, void* d_out, size_t cap, void* stream) { return serialize_device<T>(impl<T, D>(b), d_out, cap, stream); } \
+    bvh##S* bvh##S##_deserialize_device(const void* d_bytes, size_t size, void* stream) {                           \
+        return handle<T, D>(deserialize_from_device<T>(d_bytes, size, D, static_cast<hipStream_t>(stream))); }      \
+    bvh_node##S* bvh##S##_get_node(bvh##S* b, size_t i) { return get_node<T, D>(impl<T, D>(b), i); }                \
+    size_t bvh##S##_get_prim_id(const bvh##S* b, size_t i) { return get_prim_id<T>(impl<T, D>(b), i); }             \
+    size_t bvh##S##_get_prim_count(const bvh##S* b) { return impl<T, D>(b)->prim_count; }                           \
+    size_t bvh##S##_get_node_count(const bvh##S* b) { return impl<T, D>(b)->node_count; }                           \
+    bool bvh_node##S##_is_leaf(const bvh_node##S* n) { return is_leaf<T, D>(n); }                                   \
+    size_t bvh_node##S##_get_prim_count(const bvh_node##S* n) { return get_prim_count<T, D>(n); }                   \
+    size_t bvh_node##S##_get_first_id(const bvh_node##S* n) { return get_first_id<T, D>(n); }                       \
+    bvh_bbox##S bvh_node##S##_get_bbox(const bvh_node##S* n) { return get_bbox<T, D>(n); }                          \
+    void bvh##S##_copy_nodes(const bvh##S* b, void* out) { copy_nodes<T, D>(impl<T, D>(b), out); }                  \
+    void bvh##S##_copy_prim_ids(const bvh##S* b, size_t* out) { copy_prim_ids<T>(impl<T, D>(b), out); }             \
+    const uint32_t* bvh##S##_device_prim_ids(const bvh##S* b) { return impl<T, D>(b)->d_prim_ids; }                 \
+    int bvh_amd_sphere_bounds##S(const T* sp, size_t n, T* bb, T* cc, void* s) {                                    \
+        return Family<T, D>::sphere_bounds(sp, n, bb, cc, static_cast<hipStream_t>(s)); }                           \
+    int bvh##S##_intersect_rays_sphere(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, unsigned flags, \
+                                       HitOf<T>::Type* hits, bvh_amd_counters* cnt, void* s) {                      \
+        return intersect<T, D>(b, LEAF_SPHERE, prims, rays, n, flags, hits, cnt, s); }
+
+// What only `3f` / `3d` export: triangles (tri.h), the mini-tree grid, the 3D area term, and the point queries.
+#define BVH_AMD_IMPL_3D(T, S)                                                                                       \
     bvh##S* bvh##S##_build_minitree_device(const T* d_bb, const T* d_cc, size_t n, const bvh_amd_minitree_config* cfg, void* stream) { \
         return build_minitree<T>(d_bb, d_cc, n, cfg, stream); }                                                     \
-    bvh##S* bvh##S##_extract(bvh##S* b, size_t root_id) { return handle<T>(extract<T>(impl<T>(b), root_id)); }      \
-    bvh##S* bvh##S##_from_nodes(const void* nodes, size_t nn, const size_t* ids, size_t np) {                       \
-        return from_nodes<T>(nodes, nn, ids, np); }                                                                 \
-    void bvh##S##_destroy(bvh##S* b) { delete impl<T>(b); }                                                         \
-    void bvh##S##_optimize(bvh_thread_pool*, bvh##S* b) { loud_or_abort(optimize<T>(impl<T>(b)), "bvh" #S "_optimize"); } \
-    int bvh##S##_optimize_config(bvh##S* b, const bvh_amd_optimize_config* c) { return optimize_config<T>(impl<T>(b), c); } \
-    void bvh##S##_refit(bvh##S* b) { loud_or_abort(refit<T>(impl<T>(b)), "bvh" #S "_refit"); }                     \
-    int bvh##S##_refit_status(bvh##S* b) { return refit<T>(impl<T>(b)); }                                           \
-    int bvh##S##_sync_device(bvh##S* b) { return sync_device<T>(impl<T>(b)); }                                       \
-    int bvh##S##_refit_boxes(bvh##S* b, const T* d_bb, size_t n, void* s) {                                         \
-        return refit_prims<T>(impl<T>(b), REFIT_BOXES3, d_bb, n, nullptr, s, "refit_boxes"); }                       \
     int bvh##S##_refit_tris(bvh##S* b, const T* d_tris9, size_t n, T* d_tris12_out, void* s) {                      \
-        return refit_prims<T>(impl<T>(b), REFIT_TRIS, d_tris9, n, d_tris12_out, s, "refit_tris"); }                  \
-    int bvh##S##_traversal_cost(bvh##S* b, double* cost_out, void* s) { return traversal_cost_checked<T>(impl<T>(b), cost_out, s); } \
-    void bvh##S##_append_node(bvh##S* b) {                                                                          \
-        if (impl<T>(b)->sync_host() != BVH_AMD_OK) return;                                                           \
-        impl<T>(b)->nodes.emplace_back(); impl<T>(b)->node_count = impl<T>(b)->nodes.size(); }                       \
-    void bvh##S##_remove_last_node(bvh##S* b) {                                                                     \
-        if (impl<T>(b)->sync_host() != BVH_AMD_OK || impl<T>(b)->nodes.empty()) return;                              \
-        impl<T>(b)->nodes.pop_back(); impl<T>(b)->node_count = impl<T>(b)->nodes.size(); }                           \
-    void bvh_node##S##_set_prim_count(bvh_node##S* n, size_t c) {                                                   \
-        auto h = reinterpret_cast<HostNode<T>*>(n);                                                                 \
-        h->index = (h->index & ~static_cast<IndexOf<T>::Type>(kCountMask)) | (static_cast<IndexOf<T>::Type>(c) & kCountMask); } \
-    void bvh_node##S##_set_first_id(bvh_node##S* n, size_t f) {                                                     \
-        auto h = reinterpret_cast<HostNode<T>*>(n);                                                                 \
-        h->index = (static_cast<IndexOf<T>::Type>(f) << kCountBits) | (h->index & kCountMask); }                    \
-    void bvh_node##S##_set_bbox(bvh_node##S* n, const bvh_bbox##S* bb) {                                            \
-        auto h = reinterpret_cast<HostNode<T>*>(n);                                                                 \
-        h->bounds[0] = bb->min.x; h->bounds[1] = bb->max.x; h->bounds[2] = bb->min.y; h->bounds[3] = bb->max.y;     \
-        h->bounds[4] = bb->min.z; h->bounds[5] = bb->max.z; }                                                         \
-    void bvh##S##_save(const bvh##S* b, FILE* f) { if (b && f) save<T>(*impl<T>(b), f); }                           \
-    bvh##S* bvh##S##_load(FILE* f) { return f ? load<T>(f) : nullptr; }                                             \
-    size_t bvh##S##_serialize(const bvh##S* b, void* out, size_t cap) { return b ? serialize<T>(*impl<T>(b), out, cap) : 0; } \
-    bvh##S* bvh##S##_deserialize(const void* bytes, size_t size) { return deserialize<T>(bytes, size); }            \
-    size_t bvh##S##_serialize_device(bvh##S* b, void* d_out, size_t cap, void* stream) { return serialize_device<T>(impl<T>(b), d_out, cap, stream); } \
-    bvh##S* bvh##S##_deserialize_device(const void* d_bytes, size_t size, void* stream) {                           \
-        return handle<T>(deserialize_from_device<T>(d_bytes, size, 3, static_cast<hipStream_t>(stream))); }         \
-    bvh_node##S* bvh##S##_get_node(bvh##S* b, size_t i) {                                                          \
-        if (impl<T>(b)->sync_host() != BVH_AMD_OK) return nullptr;                                                   \
-        return reinterpret_cast<bvh_node##S*>(&impl<T>(b)->nodes[i]); }                                              \
-    size_t bvh##S##_get_prim_id(const bvh##S* b, size_t i) {                                                        \
-        if (impl<T>(b)->sync_host() != BVH_AMD_OK) return BVH_INVALID_PRIM_ID;                                       \
-        return impl<T>(b)->prim_ids[i]; }                                                                            \
-    size_t bvh##S##_get_prim_count(const bvh##S* b) { return impl<T>(b)->prim_count; }                              \
-    size_t bvh##S##_get_node_count(const bvh##S* b) { return impl<T>(b)->node_count; }                              \
-    bool bvh_node##S##_is_leaf(const bvh_node##S* n) { return (reinterpret_cast<const HostNode<T>*>(n)->index & kCountMask) != 0; } \
-    size_t bvh_node##S##_get_prim_count(const bvh_node##S* n) { return reinterpret_cast<const HostNode<T>*>(n)->index & kCountMask; } \
-    size_t bvh_node##S##_get_first_id(const bvh_node##S* n) { return reinterpret_cast<const HostNode<T>*>(n)->index >> kCountBits; } \
-    bvh_bbox##S bvh_node##S##_get_bbox(const bvh_node##S* n) {                                                      \
-        auto h = reinterpret_cast<const HostNode<T>*>(n);                                                           \
-        bvh_bbox##S r; r.min.x = h->bounds[0]; r.max.x = h->bounds[1]; r.min.y = h->bounds[2]; r.max.y = h->bounds[3]; \
-        r.min.z = h->bounds[4]; r.max.z = h->bounds[5]; return r; }                                                 \
-    void bvh##S##_copy_nodes(const bvh##S* b, void* out) {                                                          \
-        if (impl<T>(b)->sync_host() != BVH_AMD_OK) return;                                                           \
-        std::memcpy(out, impl<T>(b)->nodes.data(), impl<T>(b)->nodes.size() * sizeof(HostNode<T>)); }               \
-    void bvh##S##_copy_prim_ids(const bvh##S* b, size_t* out) {                                                     \
-        if (impl<T>(b)->sync_host() != BVH_AMD_OK) return;                                                           \
-        std::memcpy(out, impl<T>(b)->prim_ids.data(), impl<T>(b)->prim_ids.size() * sizeof(size_t)); }              \
-    const uint32_t* bvh##S##_device_prim_ids(const bvh##S* b) { return impl<T>(b)->d_prim_ids; }                    \
+        return refit_prims<T>(impl<T, 3>(b), REFIT_TRIS, d_tris9, n, d_tris12_out, s, "refit_tris"); }               \
+    int bvh##S##_traversal_cost(bvh##S* b, double* cost_out, void* s) { return traversal_cost_checked<T>(impl<T, 3>(b), cost_out, s); } \
+    int bvh##S##_prepare_trace(const bvh##S* b, size_t n_rays_hint, void* s) { return prepare_trace_checked<T>(impl<T, 3>(b), n_rays_hint, s); } \
     int bvh_amd_tri_bounds##S(const T* t, size_t n, T* bb, T* cc, void* s) {                                        \
         return launch_tri_bounds<T>(t, n, bb, cc, static_cast<hipStream_t>(s)); }                                   \
     int bvh_amd_precompute_tris##S(const T* t, const uint32_t* perm, size_t n, T* out, void* s) {                   \
         return launch_precompute_tris<T>(t, perm, n, out, static_cast<hipStream_t>(s)); }                           \
-    int bvh_amd_sphere_bounds##S(const T* sp, size_t n, T* bb, T* cc, void* s) {                                    \
-        return launch_sphere_bounds<T>(sp, n, bb, cc, static_cast<hipStream_t>(s)); }                               \
     int bvh##S##_intersect_rays_tri(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, unsigned flags, \
                                     bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                             \
-        return intersect<T>(b, LEAF_TRIANGLE, prims, rays, n, flags, hits, cnt, s); }                               \
-    int bvh##S##_intersect_rays_sphere(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, unsigned flags, \
-                                       bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                          \
-        return intersect<T>(b, LEAF_SPHERE, prims, rays, n, flags, hits, cnt, s); }                                 \
+        return intersect<T, 3>(b, LEAF_TRIANGLE, prims, rays, n, flags, hits, cnt, s); }                            \
     int bvh##S##_closest_points_tri(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned flags,       \
                                     bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                             \
         return closest<T>(b, LEAF_TRIANGLE, prims, queries, n, flags, hits, cnt, s); }                              \
@@ -796,115 +771,30 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
         return knn<T>(b, LEAF_TRIANGLE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }        \
     int bvh##S##_knn_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned k, unsigned flags, uint32_t* out_prims, \
                             T* out_dist, uint32_t* counts, bvh_amd_counters* cnt, void* s) {                        \
-        return knn<T>(b, LEAF_SPHERE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }          \
-    int bvh##S##_prepare_trace(const bvh##S* b, size_t n_rays_hint, void* s) {                                      \
-        if (!b) return fail(BVH_AMD_ERR_ARG, "prepare_trace: null bvh");                                            \
-        int cur = -1;                                                                                               \
-        BVH_HIP_TRY(hipGetDevice(&cur), BVH_AMD_ERR_HIP);                                                           \
-        if (cur != impl<T>(b)->device) return fail(BVH_AMD_ERR_ARG, "prepare_trace: BVH lives on another device than the current one"); \
-        return prepare_trace<T>(*impl<T>(b), n_rays_hint, static_cast<hipStream_t>(s)); }
+        return knn<T>(b, LEAF_SPHERE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }
 
-BVH_AMD_IMPL(float, 3f)
-BVH_AMD_IMPL(double, 3d)
-
-#define BVH_AMD_IMPL_RAY(T, S, CB, VIS, D, IMPL)                                                                         \
-    void bvh##S##_intersect_ray(const bvh##S* b, const bvh_ray##S* r, const CB* cb) { intersect_ray_legacy<T, D>(IMPL<T>(b), r, cb, 0u); } \
+#define BVH_AMD_IMPL_RAY(T, D, S, CB, VIS)                                                                          \
+    void bvh##S##_intersect_ray(const bvh##S* b, const bvh_ray##S* r, const CB* cb) { intersect_ray_legacy<T, D>(impl<T, D>(b), r, cb, 0u); } \
     void bvh##S##_intersect_ray_any(const bvh##S* b, const bvh_ray##S* r, const CB* cb) {                           \
-        intersect_ray_legacy<T, D>(IMPL<T>(b), r, cb, BVH_AMD_RAY_ANY_HIT); }                                        \
+        intersect_ray_legacy<T, D>(impl<T, D>(b), r, cb, BVH_AMD_RAY_ANY_HIT); }                                     \
     void bvh##S##_intersect_ray_robust(const bvh##S* b, const bvh_ray##S* r, const CB* cb) {                        \
-        intersect_ray_legacy<T, D>(IMPL<T>(b), r, cb, BVH_AMD_RAY_ROBUST); }                                         \
+        intersect_ray_legacy<T, D>(impl<T, D>(b), r, cb, BVH_AMD_RAY_ROBUST); }                                      \
     void bvh##S##_intersect_ray_any_robust(const bvh##S* b, const bvh_ray##S* r, const CB* cb) {                    \
-        intersect_ray_legacy<T, D>(IMPL<T>(b), r, cb, BVH_AMD_RAY_ANY_HIT | BVH_AMD_RAY_ROBUST); }                   \
+        intersect_ray_legacy<T, D>(impl<T, D>(b), r, cb, BVH_AMD_RAY_ANY_HIT | BVH_AMD_RAY_ROBUST); }                \
     int bvh##S##_intersect_ray_visit(const bvh##S* b, const bvh_ray##S* r, size_t start, unsigned flags, const VIS* v) { \
         if (!v || !v->leaf_fn) return fail(BVH_AMD_ERR_ARG, "intersect_ray_visit: null visitor");                   \
-        return intersect_ray_visit<T, D>(IMPL<T>(b), r, start, flags, v->leaf_fn, v->inner_fn, v->user_data); }
+        return intersect_ray_visit<T, D>(impl<T, D>(b), r, start, flags, v->leaf_fn, v->inner_fn, v->user_data); }
 
-BVH_AMD_IMPL_RAY(float, 3f, bvh_intersect_callbackf, bvh_amd_ray_visitorf, 3, impl)
-BVH_AMD_IMPL_RAY(double, 3d, bvh_intersect_callbackd, bvh_amd_ray_visitord, 3, impl)
-
-#define BVH_AMD_IMPL2(T, S)                                                                                         \
-    bvh##S* bvh##S##_build(bvh_thread_pool* pool, const bvh_bbox##S* bb, const bvh_vec##S* cc, size_t n,            \
-                           const bvh_build_config* cfg) { return loud(build2_host<T>(pool, bb, cc, n, cfg), "bvh" #S "_build"); } \
-    bvh##S* bvh##S##_build_device(const T* d_bb4, const T* d_cc2, size_t n, const bvh_build_config* cfg,            \
-                                  enum bvh_amd_builder builder, void* stream) {                                     \
-        return build2_device<T>(d_bb4, d_cc2, n, cfg, builder, stream); }                                           \
-    bvh##S* bvh##S##_build_sah(bvh_thread_pool* pool, const bvh_bbox##S* bb, const bvh_vec##S* cc, size_t n,        \
-                               const bvh_build_config* cfg, const bvh_amd_sah_config* sah) {                       \
-        return with_sah(sah, [&] { return build2_host<T>(pool, bb, cc, n, cfg); }); }                               \
-    bvh##S* bvh##S##_build_device_sah(const T* d_bb4, const T* d_cc2, size_t n, const bvh_build_config* cfg,        \
-                                      enum bvh_amd_builder builder, const bvh_amd_sah_config* sah, void* stream) {  \
-        return with_sah(sah, [&] { return build2_device<T>(d_bb4, d_cc2, n, cfg, builder, stream); }); }            \
-    bvh##S* bvh##S##_build_device_binned(const T* d_bb4, const T* d_cc2, size_t n, const bvh_build_config* cfg,     \
-                                         const bvh_amd_sah_config* sah, size_t bin_count, void* stream) {           \
-        return with_bins(sah, bin_count, [&] { return build2_device<T>(d_bb4, d_cc2, n, cfg, BVH_AMD_BUILDER_BINNED, stream); }); } \
-    bvh##S* bvh##S##_extract(bvh##S* b, size_t root_id) { return handle2<T>(extract<T>(impl2<T>(b), root_id)); }    \
-    bvh##S* bvh##S##_from_nodes(const void* nodes, size_t nn, const size_t* ids, size_t np) {                       \
-        return from_nodes2<T>(nodes, nn, ids, np); }                                                                \
-    void bvh##S##_destroy(bvh##S* b) { delete impl2<T>(b); }                                                        \
-    void bvh##S##_optimize(bvh_thread_pool*, bvh##S* b) { loud_or_abort(optimize<T>(impl2<T>(b)), "bvh" #S "_optimize"); } \
-    int bvh##S##_optimize_config(bvh##S* b, const bvh_amd_optimize_config* c) { return optimize_config<T>(impl2<T>(b), c); } \
-    void bvh##S##_refit(bvh##S* b) { loud_or_abort(refit<T>(impl2<T>(b)), "bvh" #S "_refit"); }                    \
-    int bvh##S##_refit_status(bvh##S* b) { return refit<T>(impl2<T>(b)); }                                          \
-    int bvh##S##_sync_device(bvh##S* b) { return sync_device<T>(impl2<T>(b)); }                                      \
-    int bvh##S##_refit_boxes(bvh##S* b, const T* d_bb4, size_t n, void* s) {                                        \
-        return refit_prims<T>(impl2<T>(b), REFIT_BOXES2, d_bb4, n, nullptr, s, "refit_boxes"); }                     \
-    void bvh##S##_append_node(bvh##S* b) {                                                                          \
-        if (impl2<T>(b)->sync_host2() != BVH_AMD_OK) return;                                                         \
-        impl2<T>(b)->nodes2.emplace_back(); impl2<T>(b)->node_count = impl2<T>(b)->nodes2.size(); }                  \
-    void bvh##S##_remove_last_node(bvh##S* b) {                                                                     \
-        if (impl2<T>(b)->sync_host2() != BVH_AMD_OK || impl2<T>(b)->nodes2.empty()) return;                          \
-        impl2<T>(b)->nodes2.pop_back(); impl2<T>(b)->node_count = impl2<T>(b)->nodes2.size(); }                      \
-    void bvh_node##S##_set_prim_count(bvh_node##S* n, size_t c) {                                                   \
-        auto h = reinterpret_cast<HostNode2<T>*>(n);                                                                \
-        h->index = (h->index & ~static_cast<IndexOf<T>::Type>(kCountMask)) | (static_cast<IndexOf<T>::Type>(c) & kCountMask); } \
-    void bvh_node##S##_set_first_id(bvh_node##S* n, size_t f) {                                                     \
-        auto h = reinterpret_cast<HostNode2<T>*>(n);                                                                \
-        h->index = (static_cast<IndexOf<T>::Type>(f) << kCountBits) | (h->index & kCountMask); }                    \
-    void bvh_node##S##_set_bbox(bvh_node##S* n, const bvh_bbox##S* bb) {                                            \
-        auto h = reinterpret_cast<HostNode2<T>*>(n);                                                                \
-        h->bounds[0] = bb->min.x; h->bounds[1] = bb->max.x; h->bounds[2] = bb->min.y; h->bounds[3] = bb->max.y; }   \
-    void bvh##S##_save(const bvh##S* b, FILE* f) {                                                                  \
-        if (!b || !f) return;                                                                                        \
-        std::vector<uint8_t> buf(stream_size2(*impl2<T>(b)));                                                        \
-        serialize2(*impl2<T>(b), buf.data(), buf.size());                                                            \
-        fwrite(buf.data(), 1, buf.size(), f); }                                                                      \
-    bvh##S* bvh##S##_load(FILE* f) { return f ? load2<T>(f) : nullptr; }                                            \
-    size_t bvh##S##_serialize(const bvh##S* b, void* out, size_t cap) { return b ? serialize2<T>(*impl2<T>(b), out, cap) : 0; } \
-    bvh##S* bvh##S##_deserialize(const void* bytes, size_t size) { return deserialize2<T>(bytes, size); }           \
-    size_t bvh##S##_serialize_device(bvh##S* b, void* d_out, size_t cap, void* stream) { return serialize_device<T>(impl2<T>(b), d_out, cap, stream); } \
-    bvh##S* bvh##S##_deserialize_device(const void* d_bytes, size_t size, void* stream) {                           \
-        return handle2<T>(deserialize_from_device<T>(d_bytes, size, 2, static_cast<hipStream_t>(stream))); }        \
-    bvh_node##S* bvh##S##_get_node(bvh##S* b, size_t i) {                                                          \
-        if (impl2<T>(b)->sync_host2() != BVH_AMD_OK) return nullptr;                                                 \
-        return reinterpret_cast<bvh_node##S*>(&impl2<T>(b)->nodes2[i]); }                                            \
-    size_t bvh##S##_get_prim_id(const bvh##S* b, size_t i) {                                                        \
-        if (impl2<T>(b)->sync_host() != BVH_AMD_OK) return BVH_INVALID_PRIM_ID;                                      \
-        return impl2<T>(b)->prim_ids[i]; }                                                                           \
-    size_t bvh##S##_get_prim_count(const bvh##S* b) { return impl2<T>(b)->prim_count; }                             \
-    size_t bvh##S##_get_node_count(const bvh##S* b) { return impl2<T>(b)->node_count; }                             \
-    bool bvh_node##S##_is_leaf(const bvh_node##S* n) { return (reinterpret_cast<const HostNode2<T>*>(n)->index & kCountMask) != 0; } \
-    size_t bvh_node##S##_get_prim_count(const bvh_node##S* n) { return reinterpret_cast<const HostNode2<T>*>(n)->index & kCountMask; } \
-    size_t bvh_node##S##_get_first_id(const bvh_node##S* n) { return reinterpret_cast<const HostNode2<T>*>(n)->index >> kCountBits; } \
-    bvh_bbox##S bvh_node##S##_get_bbox(const bvh_node##S* n) {                                                      \
-        auto h = reinterpret_cast<const HostNode2<T>*>(n);                                                          \
-        bvh_bbox##S r; r.min.x = h->bounds[0]; r.max.x = h->bounds[1]; r.min.y = h->bounds[2]; r.max.y = h->bounds[3]; return r; } \
-    void bvh##S##_copy_nodes(const bvh##S* b, void* out) {                                                          \
-        if (impl2<T>(b)->sync_host2() != BVH_AMD_OK) return;                                                         \
-        std::memcpy(out, impl2<T>(b)->nodes2.data(), impl2<T>(b)->nodes2.size() * sizeof(HostNode2<T>)); }          \
-    void bvh##S##_copy_prim_ids(const bvh##S* b, size_t* out) {                                                     \
-        if (impl2<T>(b)->sync_host() != BVH_AMD_OK) return;                                                          \
-        std::memcpy(out, impl2<T>(b)->prim_ids.data(), impl2<T>(b)->prim_ids.size() * sizeof(size_t)); }            \
-    const uint32_t* bvh##S##_device_prim_ids(const bvh##S* b) { return impl2<T>(b)->d_prim_ids; }                   \
-    int bvh_amd_sphere_bounds##S(const T* c3, size_t n, T* bb4, T* cc2, void* s) {                                  \
-        return launch_circle_bounds<T>(c3, n, bb4, cc2, static_cast<hipStream_t>(s)); }                             \
-    int bvh##S##_intersect_rays_sphere(const bvh##S* b, const T* circles, const bvh_ray##S* rays, size_t n, unsigned flags, \
-                                       HitOf<T>::Type* hits, bvh_amd_counters* cnt, void* s) {                      \
-        return intersect2<T>(b, circles, rays, n, flags, hits, cnt, s); }
-
-BVH_AMD_IMPL2(float, 2f)
-BVH_AMD_IMPL2(double, 2d)
-BVH_AMD_IMPL_RAY(float, 2f, bvh_intersect_callbackf, bvh_amd_ray_visitorf, 2, impl2)
-BVH_AMD_IMPL_RAY(double, 2d, bvh_intersect_callbackd, bvh_amd_ray_visitord, 2, impl2)
+BVH_AMD_IMPL(float, 3, 3f)
+BVH_AMD_IMPL(double, 3, 3d)
+BVH_AMD_IMPL(float, 2, 2f)
+BVH_AMD_IMPL(double, 2, 2d)
+BVH_AMD_IMPL_3D(float, 3f)
+BVH_AMD_IMPL_3D(double, 3d)
+BVH_AMD_IMPL_RAY(float, 3, 3f, bvh_intersect_callbackf, bvh_amd_ray_visitorf)
+BVH_AMD_IMPL_RAY(double, 3, 3d, bvh_intersect_callbackd, bvh_amd_ray_visitord)
+BVH_AMD_IMPL_RAY(float, 2, 2f, bvh_intersect_callbackf, bvh_amd_ray_visitorf)
+BVH_AMD_IMPL_RAY(double, 2, 2d, bvh_intersect_callbackd, bvh_amd_ray_visitord)
 
 int bvh_amd_offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets, void* stream) {
     return offsets_from_counts(d_counts, n, d_offsets, static_cast<hipStream_t>(stream));
@@ -916,14 +806,12 @@ int bvh_amd_std_sort_ids3d(const double* d_keys, size_t n, uint32_t* d_ids_out, 
     return std_sort_ids<double>(d_ids_out, d_keys, static_cast<uint32_t>(n), 1, 0, 1, static_cast<hipStream_t>(stream));
 }
 int bvh_amd_radix_sort_pairs_u32(uint32_t* d_keys, uint32_t* d_vals, size_t n, int bits, void* stream) {
-    uint32_t *kt = nullptr, *vt = nullptr;
+    DeviceTemps<uint32_t> tmp;
+    auto& [kt, vt] = tmp;
     BVH_HIP_TRY(hipMalloc(&kt, std::max<size_t>(n, 1) * 4), BVH_AMD_ERR_HIP);
     hipError_t e = hipMalloc(&vt, std::max<size_t>(n, 1) * 4);
-    int rc = e == hipSuccess ? radix_sort_pairs<uint32_t>(d_keys, d_vals, kt, vt, static_cast<uint32_t>(n), 1, bits, static_cast<hipStream_t>(stream))
-                             : fail(BVH_AMD_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(kt);
-    if (vt) (void)hipFree(vt);
-    return rc;
+    return e == hipSuccess ? radix_sort_pairs<uint32_t>(d_keys, d_vals, kt, vt, static_cast<uint32_t>(n), 1, bits, static_cast<hipStream_t>(stream))
+                           : fail(BVH_AMD_ERR_HIP, hipGetErrorString(e));
 }
 
 int bvh_amd_pinhole_rays3f(const float eye[3], const float dir[3], const float up[3], size_t w, size_t h, bvh_ray3f* d_rays, void* stream) {

@@ -18,6 +18,46 @@ def _lib():
     return _lib, _lib.load()
 
 
+NODE_BYTES = {"3f": 28, "3d": 56, "2f": 20, "2d": 40}
+
+
+def _serialized(dll, sfx, h):
+    n = getattr(dll, f"bvh{sfx}_serialize")(h, None, 0)
+    buf = C.create_string_buffer(n)
+    assert getattr(dll, f"bvh{sfx}_serialize")(h, buf, n) == n
+    return buf.raw
+
+
+def _check_file_round_trip_and_copies(dll, sfx, h, want, tmp_path):
+    """FILE* round trip in the reference's byte format (c_api/bvh.h:136-144), and bvhXX_copy_nodes / _copy_prim_ids against the
+    payload of the stream `want` that bvhXX_serialize gave for `h`."""
+    libc = C.CDLL(None)
+    libc.fopen.restype, libc.fopen.argtypes = C.c_void_p, [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    path = str(tmp_path / "bvh.bin").encode()
+    f = libc.fopen(path, b"wb")
+    getattr(dll, f"bvh{sfx}_save")(h, f)
+    libc.fclose(f)
+    assert open(path, "rb").read() == want
+    f = libc.fopen(path, b"rb")
+    h2 = getattr(dll, f"bvh{sfx}_load")(f)
+    libc.fclose(f)
+    assert h2
+    assert _serialized(dll, sfx, h2) == want
+    getattr(dll, f"bvh{sfx}_destroy")(h2)
+    idx_dt = np.dtype("<u4" if sfx[1] == "f" else "<u8")
+    nn, npr = (int(v) for v in np.frombuffer(want, dtype=idx_dt, count=2))
+    assert nn == getattr(dll, f"bvh{sfx}_get_node_count")(h) and npr == getattr(dll, f"bvh{sfx}_get_prim_count")(h)
+    off = 2 * idx_dt.itemsize
+    nodes = C.create_string_buffer(nn * NODE_BYTES[sfx])
+    getattr(dll, f"bvh{sfx}_copy_nodes")(h, nodes)
+    assert nodes.raw == want[off:off + len(nodes)]
+    ids = np.full(npr, 2**64 - 1, dtype=np.uint64)                        # size_t
+    getattr(dll, f"bvh{sfx}_copy_prim_ids")(h, ids.ctypes.data_as(C.c_void_p))
+    assert off + len(nodes) + npr * idx_dt.itemsize == len(want)
+    assert (ids == np.frombuffer(want, dtype=idx_dt, count=npr, offset=off + len(nodes))).all()
+
+
 @pytest.mark.parametrize("sfx,scene", [("3f", "soup2k"), ("3d", "soup2k_f64")])
 @pytest.mark.parametrize("quality,pool,key", [(0, False, "serial_low"), (1, False, "serial_med"), (2, False, "serial_high"),
                                                (0, True, "parallel_low"), (1, True, "parallel_med"), (2, True, "parallel_high")])
@@ -56,28 +96,67 @@ def test_bvhXX_build_host_pointers(sfx, scene, quality, pool, key, tmp_path):
             assert (got[:3] == ref_nodes["bounds"][i][0::2]).all() and (got[3:] == ref_nodes["bounds"][i][1::2]).all()
         for i in (0, npr // 3, npr - 1):
             assert getattr(dll, f"bvh{sfx}_get_prim_id")(h, i) == int(ref_ids[i])
-        # FILE* round trip in the reference's byte format (c_api/bvh.h:136-144)
-        libc = C.CDLL(None)
-        libc.fopen.restype, libc.fopen.argtypes = C.c_void_p, [C.c_char_p, C.c_char_p]
-        libc.fclose.argtypes = [C.c_void_p]
-        path = str(tmp_path / "bvh.bin").encode()
-        f = libc.fopen(path, b"wb")
-        getattr(dll, f"bvh{sfx}_save")(h, f)
-        libc.fclose(f)
-        assert open(path, "rb").read() == want
-        f = libc.fopen(path, b"rb")
-        h2 = getattr(dll, f"bvh{sfx}_load")(f)
-        libc.fclose(f)
-        assert h2
-        n2 = getattr(dll, f"bvh{sfx}_serialize")(h2, None, 0)
-        buf2 = C.create_string_buffer(n2)
-        getattr(dll, f"bvh{sfx}_serialize")(h2, buf2, n2)
-        assert buf2.raw == want
-        getattr(dll, f"bvh{sfx}_destroy")(h2)
+        _check_file_round_trip_and_copies(dll, sfx, h, want, tmp_path)
     finally:
         getattr(dll, f"bvh{sfx}_destroy")(h)
         if tp:
             dll.bvh_thread_pool_destroy(tp)
+
+
+@pytest.mark.parametrize("sfx,scene", [("2f", "circles2k_2f"), ("2d", "circles2k_2d")])
+def test_bvh2X_file_round_trip_and_copies(sfx, scene, tmp_path):
+    """The 2D families' save / load / copy_nodes / copy_prim_ids, on their 20/40-byte nodes, like test_bvhXX_build_host_pointers for 3D."""
+    L, dll = _lib()
+    g = load_golden(scene)
+    bb, cc = np.ascontiguousarray(g["bboxes"]), np.ascontiguousarray(g["centers"])
+    h = getattr(dll, f"bvh{sfx}_build")(None, bb.ctypes.data_as(C.c_void_p), cc.ctypes.data_as(C.c_void_p), len(bb), None)
+    assert h, L.last_error()
+    try:
+        want = g["bvh_serial_high"].tobytes()                          # NULL config = Quality::High
+        assert _serialized(dll, sfx, h) == want
+        _check_file_round_trip_and_copies(dll, sfx, h, want, tmp_path)
+    finally:
+        getattr(dll, f"bvh{sfx}_destroy")(h)
+
+
+@pytest.mark.parametrize("sfx", ["3f", "3d"])
+def test_3d_raw_c_abi_mirror_editing(sfx):
+    """The node editing API of c_api/bvh.h:170-218 on the 28/56-byte mirror, as tests/test_gpu_2d.py does for the 2D families: append a
+    node, fill it through the setters, read it back through the getters, remove it again: the stream is unchanged after sync_device."""
+    L, dll = _lib()
+    g = load_golden("cornell")
+    dt, ct = (np.float32, C.c_float) if sfx == "3f" else (np.float64, C.c_double)
+    bb, cc = np.ascontiguousarray(g["bboxes"], dtype=dt), np.ascontiguousarray(g["centers"], dtype=dt)
+    h = getattr(dll, f"bvh{sfx}_build")(None, bb.ctypes.data_as(C.c_void_p), cc.ctypes.data_as(C.c_void_p), len(bb), None)
+    assert h, L.last_error()
+    try:
+        before = _serialized(dll, sfx, h)
+        if sfx == "3f":
+            assert before == g["bvh_serial_high"].tobytes()
+        nn = getattr(dll, f"bvh{sfx}_get_node_count")(h)
+        assert 16 < nn < 100
+        getattr(dll, f"bvh{sfx}_append_node")(h)
+        assert getattr(dll, f"bvh{sfx}_get_node_count")(h) == nn + 1
+        node = getattr(dll, f"bvh{sfx}_get_node")(h, nn)
+        box = [0.25, 0.5, 0.75, 1.0, 1.25, 1.5]                          # {min.x, min.y, min.z, max.x, max.y, max.z}
+        getattr(dll, f"bvh_node{sfx}_set_bbox")(node, (ct * 6)(*box))
+        getattr(dll, f"bvh_node{sfx}_set_first_id")(node, 7)
+        getattr(dll, f"bvh_node{sfx}_set_prim_count")(node, 3)
+        assert getattr(dll, f"bvh_node{sfx}_is_leaf")(node) and getattr(dll, f"bvh_node{sfx}_get_prim_count")(node) == 3
+        assert getattr(dll, f"bvh_node{sfx}_get_first_id")(node) == 7
+        assert list(getattr(dll, f"bvh_node{sfx}_get_bbox")(node).v) == box
+        edited = C.create_string_buffer((nn + 1) * NODE_BYTES[sfx])     # the node's own layout: {min, max} per axis, then the index word
+        getattr(dll, f"bvh{sfx}_copy_nodes")(h, edited)
+        last = np.frombuffer(edited.raw[nn * NODE_BYTES[sfx]:], dtype=oracle.NODEF if sfx == "3f" else oracle.NODED)[0]
+        assert list(last["bounds"]) == [0.25, 1.0, 0.5, 1.25, 0.75, 1.5] and int(last["index"]) == (7 << 4 | 3)
+        getattr(dll, f"bvh_node{sfx}_set_prim_count")(node, 0)         # the count alone: the first id stays
+        assert not getattr(dll, f"bvh_node{sfx}_is_leaf")(node) and getattr(dll, f"bvh_node{sfx}_get_first_id")(node) == 7
+        getattr(dll, f"bvh{sfx}_remove_last_node")(h)
+        assert getattr(dll, f"bvh{sfx}_get_node_count")(h) == nn
+        assert getattr(dll, f"bvh{sfx}_sync_device")(h) == 0, L.last_error()
+        assert _serialized(dll, sfx, h) == before
+    finally:
+        getattr(dll, f"bvh{sfx}_destroy")(h)
 
 
 def test_null_config_means_reference_defaults(orc):

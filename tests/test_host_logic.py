@@ -218,3 +218,77 @@ def test_release_library_reads_only_the_documented_environment():
     enum_like = {n for n in names if re.search(r"\b" + n + r"\b\s*=", header) or ("#define " + n) in header}
     assert names - enum_like <= documented, sorted(names - enum_like - documented)
     assert len(documented) <= 10
+
+
+FAMILIES = {"3f": ("<u4", 28), "3d": ("<u8", 56), "2f": ("<u4", 20), "2d": ("<u8", 40)}       # suffix -> (Index::Type, sizeof(Node<T, D>))
+
+
+def _crafted_streams(sfx):
+    """Streams whose header lies about what follows: {name: bytes}."""
+    idx, node_bytes = FAMILIES[sfx]
+    hdr = lambda nn, npr: np.array([nn, npr], dtype=idx).tobytes()
+    streams = {"one node more than the bytes hold": hdr(2, 0) + bytes(node_bytes),
+               "one id more than the bytes hold": hdr(1, 1) + bytes(node_bytes),
+               "two bytes": b"\x01\x00"}
+    if idx == "<u8":
+        # 40 * 2^61 = 5 * 2^64 and 56 * 2^61 = 7 * 2^64: the node bytes wrap to 0, so header + payload "fits" any stream of 16 bytes or more
+        assert (node_bytes << 61) % (1 << 64) == 0
+        streams["node count whose byte size wraps to zero"] = hdr(1 << 61, 0) + bytes(16)
+        streams["node count whose byte size wraps to one node"] = hdr((1 << 61) + 1, 0) + bytes(node_bytes)
+    return streams
+
+
+@pytest.mark.parametrize("sfx", sorted(FAMILIES))
+def test_crafted_stream_headers_are_refused(sfx, tmp_path):
+    """bvhXX_deserialize / bvhXX_load bound node_count and prim_count by the stream's size before they form header + nodes + ids: a
+    header that makes that sum wrap (64-bit Index, `2d` / `3d`) is "truncated" like one that is merely short — for every family, and
+    before any allocation of the claimed size or any HIP call."""
+    import ctypes as C
+    from bvh_amd import _lib, build
+    build.build()
+    dll = _lib.load()
+    libc = C.CDLL(None)
+    libc.fopen.restype, libc.fopen.argtypes = C.c_void_p, [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    for k, (name, stream) in enumerate(_crafted_streams(sfx).items()):
+        assert not getattr(dll, f"bvh{sfx}_from_nodes")(None, 0, None, 0) and "from_nodes" in _lib.last_error()     # (a known other message)
+        assert not getattr(dll, f"bvh{sfx}_deserialize")(stream, len(stream)), name
+        assert _lib.last_error() == "deserialize: truncated stream", name
+        path = tmp_path / f"{sfx}_{k}.bin"
+        path.write_bytes(stream)
+        assert not getattr(dll, f"bvh{sfx}_from_nodes")(None, 0, None, 0) and "from_nodes" in _lib.last_error()
+        f = libc.fopen(str(path).encode(), b"rb")
+        assert f
+        h = getattr(dll, f"bvh{sfx}_load")(f)
+        libc.fclose(f)
+        assert not h, name
+        assert "truncated" in _lib.last_error() or "more memory than there is" in _lib.last_error(), (name, _lib.last_error())
+
+
+@pytest.mark.parametrize("sfx", sorted(FAMILIES))
+def test_null_arguments_are_refused_with_their_messages(sfx):
+    """The argument checks in front of every family's entry points: return value and bvh_amd_last_error() text."""
+    import ctypes as C
+    from bvh_amd import _lib, build
+    build.build()
+    dll = _lib.load()
+    fn = lambda name: getattr(dll, name.format(S=sfx))
+    assert not fn("bvh{S}_build")(None, None, None, 0, None)
+    assert _lib.last_error() == "build: empty input"
+    assert not fn("bvh{S}_from_nodes")(None, 0, None, 0)
+    assert _lib.last_error() == "from_nodes: null/empty input"
+    one_node = bytes(FAMILIES[sfx][1])
+    assert not fn("bvh{S}_from_nodes")(one_node, 1, None, 3)                  # ids missing although prim_count says 3
+    assert _lib.last_error() == "from_nodes: null/empty input"
+    assert fn("bvh{S}_serialize")(None, None, 0) == 0
+    buf = C.create_string_buffer(64)
+    assert fn("bvh{S}_serialize")(None, buf, 64) == 0
+    assert fn("bvh{S}_intersect_rays_sphere")(None, None, None, 10, 0, None, None, None) == -2       # BVH_AMD_ERR_ARG
+    assert _lib.last_error() == "intersect_rays: null bvh"
+    Visitor, _, _ = _lib.ray_visitor_types(sfx)
+    ray = (C.c_double * 8)()
+    assert fn("bvh{S}_intersect_ray_visit")(None, ray, 0, 0, None) == -2
+    assert _lib.last_error() == "intersect_ray_visit: null visitor"
+    assert not fn("bvh{S}_from_nodes")(None, 0, None, 0)
+    assert fn("bvh{S}_intersect_ray_visit")(None, ray, 0, 0, C.byref(Visitor())) == -2               # a visitor without a leaf function
+    assert _lib.last_error() == "intersect_ray_visit: null visitor"
