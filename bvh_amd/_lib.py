@@ -153,6 +153,8 @@ _SIGS_T = {
     "bvh{S}_radius_search_sphere": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P, _P, _P, _P]),
     "bvh{S}_knn_tri": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_knn_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
+    "bvh{S}_overlap_boxes": (_I, [_P, _P, _Z, _P, _Z, _U, _P, _P, _P, _P, _P]),
+    "bvh{S}_overlap_self": (_I, [_P, _P, _Z, _U, _P, _P, _P, _P, _P]),
     # one ray, host leaf callback (c_api/bvh.h:277-295): (bvh, ray, callback struct)
     "bvh{S}_intersect_ray": (None, [_P, _P, _P]),
     "bvh{S}_intersect_ray_any": (None, [_P, _P, _P]),
@@ -190,6 +192,7 @@ _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_inter
             "bvh{S}_closest_points_tri", "bvh{S}_closest_points_sphere",                              # and the closest-point queries
             "bvh{S}_radius_search_tri", "bvh{S}_radius_search_sphere",                                # and the radius queries
             "bvh{S}_knn_tri", "bvh{S}_knn_sphere",                                                    # and the k-nearest queries
+            "bvh{S}_overlap_boxes", "bvh{S}_overlap_self",                                            # and the box-overlap queries
             "bvh{S}_refit_tris", "bvh{S}_traversal_cost")                                             # (tri.h; the 3D area term)
 
 

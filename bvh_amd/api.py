@@ -630,6 +630,87 @@ def radius_search(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", max_p
     return out + (cnt,) if counters else out
 
 
+def _overlap_args(bvh: Bvh, bboxes, query_boxes, who: str):
+    """The checks of the box-overlap queries: ((n_boxes, 6) boxes by original id, (n, 6) query boxes or None)."""
+    if bvh.dim != 3:
+        raise TypeError(f"{who}: 3D trees only")
+    bb = bvh._prims_in(bboxes, 6, who)
+    q = None if query_boxes is None else bvh._prims_in(query_boxes, 6, who)
+    return bb, q
+
+
+def overlap_count(bvh: Bvh, bboxes, query_boxes, sort_queries=None, counters: bool = False):
+    """For each query box, how many primitives' boxes overlap it (bvh3X_overlap_boxes without lists): an int32 (n,) tensor; with
+    counters also (pairs, box tests, leaves). bboxes: (n_boxes, 6) {min, max} indexed by ORIGINAL primitive id, what the builders and
+    refit_boxes take; query_boxes: (n, 6) in the same layout. Closed intervals: touching boxes overlap."""
+    torch = _torch()
+    bb, q = _overlap_args(bvh, bboxes, query_boxes, "overlap_count")
+    n = q.shape[0]
+    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_overlap_boxes")
+    _lib.check(fn(bvh._h, bb.data_ptr(), bb.shape[0], q.data_ptr(), n, int(_sort_flags(sort_queries)), counts.data_ptr(), None, None,
+                  cnt.data_ptr() if counters else None, _stream()), "overlap_count")
+    return (counts, cnt) if counters else counts
+
+
+def _overlap_lists(bvh: Bvh, who: str, call, n: int, dev, max_per_query, counters: bool):
+    """Count pass, offsets, fill pass (or one pass into max_per_query slots) of call(counts, offsets, ids, counters)."""
+    torch = _torch()
+    cnt = torch.zeros(3, dtype=torch.int64, device=dev) if counters else None
+    counts = torch.zeros(n, dtype=torch.int32, device=dev)
+    if max_per_query is None:
+        _lib.check(call(counts.data_ptr(), None, None, None), who)
+        offsets = offsets_from_counts(counts)
+        total = int(offsets[-1].item())
+    else:
+        k = int(max_per_query)
+        if k < 0:
+            raise ValueError("max_per_query must not be negative")
+        offsets = torch.arange(n + 1, dtype=torch.int64, device=dev) * k
+        total = n * k
+    ids = torch.empty(max(total, 1), dtype=torch.int32, device=dev)               # (never a null pointer: an empty result is still a list)
+    _lib.check(call(counts.data_ptr() if max_per_query is not None else None, offsets.data_ptr(), ids.data_ptr(), cnt.data_ptr() if counters else None), who)
+    out = (offsets, ids[:total]) if max_per_query is None else (offsets, ids[:total], counts)
+    return out + (cnt,) if counters else out
+
+
+def overlap_search(bvh: Bvh, bboxes, query_boxes, max_per_query=None, original_ids: bool = False, sort_queries=None, counters: bool = False):
+    """For each query box, the primitives whose boxes overlap it (bvh3X_overlap_boxes), in the order the tree fixes (depth-first, left
+    child first, ascending index inside a leaf). For a tree built from or refitted to `bboxes` this is exactly the brute-force set.
+    Returns (offsets, ids) as radius_search does without distances: offsets int64 (n + 1,), query q owns ids[offsets[q]:offsets[q + 1]]
+    (int32 BVH-order indices, or bvh.prim_ids[i] with original_ids).
+      max_per_query=None: exact lists - a count pass, the offsets on the device, one read of offsets[-1] to size the lists, a fill pass.
+      max_per_query=k: one pass, k slots per query (offsets = k * arange(n + 1)), unused slots holding -1 (INVALID); returns
+        (offsets, ids, counts), counts (int32, untruncated) telling which lists overflowed.
+    With counters, (pairs, box tests, leaves) of the pass that wrote the lists is appended to the result."""
+    bb, q = _overlap_args(bvh, bboxes, query_boxes, "overlap_search")
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_overlap_boxes")
+    flags = int(_sort_flags(sort_queries, original_ids))
+    n = q.shape[0]
+    call = lambda counts, offsets, ids, cnt: fn(bvh._h, bb.data_ptr(), bb.shape[0], q.data_ptr(), n, flags, counts, offsets, ids, cnt, _stream())
+    return _overlap_lists(bvh, "overlap_search", call, n, q.device, max_per_query, counters)
+
+
+def self_overlaps(bvh: Bvh, bboxes, original_ids: bool = True, counters: bool = False):
+    """Every unordered pair of primitives whose boxes overlap, once (bvh3X_overlap_self): the broad phase of a self-collision test. An
+    (m, 2) int64 device tensor; with original_ids both columns hold original primitive ids (rows of `bboxes`), otherwise BVH-order
+    indices with first < second. The rows are expanded from the CSR offsets with torch. With counters, (pairs, box tests, leaves) of
+    the fill pass is returned too."""
+    torch = _torch()
+    bb, _ = _overlap_args(bvh, bboxes, None, "self_overlaps")
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_overlap_self")
+    n = bvh.prim_count
+    call = lambda counts, offsets, ids, cnt: fn(bvh._h, bb.data_ptr(), bb.shape[0], 8 if original_ids else 0, counts, offsets, ids, cnt, _stream())
+    out = _overlap_lists(bvh, "self_overlaps", call, n, bb.device, None, counters)
+    offsets, ids = out[0], out[1]
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=bb.device), offsets[1:] - offsets[:-1])
+    if original_ids:
+        rows = bvh.device_prim_ids().long()[rows]
+    pairs = torch.stack([rows, ids.long()], dim=1)
+    return (pairs, out[2]) if counters else pairs
+
+
 KNN_MAX_K = 64                                  # BVH_AMD_KNN_MAX_K
 
 

@@ -394,9 +394,9 @@ int refit_prims(BvhImpl<T>* pb, int src_kind, const T* d_src, size_t n_src, T* d
         if (rc) return rc;
         b.max_prim_id = largest;
     }
-    if (b.prim_count && n_src <= static_cast<size_t>(b.max_prim_id))
+    if (b.prim_count && n_src <= static_cast<size_t>(b.max_prim_id.load()))
         return fail(BVH_AMD_ERR_ARG, std::string(who) + ": " + std::to_string(n_src) + " primitives given, but prim_ids refers to primitive " +
-                    std::to_string(b.max_prim_id) + " (the array is indexed by original primitive id)");
+                    std::to_string(b.max_prim_id.load()) + " (the array is indexed by original primitive id)");
     // (no wait for an earlier refit_*'s root copy here: note_refit() below supersedes it, and the host blocks on nothing in the steady
     //  state; the mirror can only be valid after sync_host(), which has waited)
     const bool from_host = b.host_valid || !b.d_nodes || b.d_nodes_count != b.node_count;
@@ -405,7 +405,7 @@ int refit_prims(BvhImpl<T>* pb, int src_kind, const T* d_src, size_t n_src, T* d
     rc = make_nodes_resident<T>(b);
     if (rc) return rc;
     if (from_host || (b.pair_count && !b.d_pairs)) {           // index words may have been edited: the records are rebuilt (and the plan with them)
-        const long long largest = b.max_prim_id;
+        const long long largest = b.max_prim_id.load();
         rc = relayout_on_device<T>(b, b.d_nodes, stream);
         if (rc) return rc;
         b.max_prim_id = largest;                               // (prim_ids cannot be edited through the mirror)
@@ -555,6 +555,18 @@ int knn(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const
     const BvhImpl<T>* b = nullptr;
     if (const int rc = point_query_tree<T>(bvh, n, "knn", &b)) return rc;
     return launch_knn<T>(*b, leaf, d_prims, d_queries4, n, k, flags, d_out_prims, d_out_dist, d_counts, d_counters, static_cast<hipStream_t>(stream));
+}
+
+// bvh3X_overlap_boxes / bvh3X_overlap_self: d_queries6 = NULL and n = the tree's primitive count in self mode.
+template <typename T>
+int overlap(const typename Family<T, 3>::Bvh* bvh, bool self, const T* d_bboxes, size_t n_boxes, const T* d_queries6, size_t n, unsigned flags,
+            uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, bvh_amd_counters* d_counters, void* stream)
+{
+    const char* who = self ? "overlap_self" : "overlap_boxes";
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, self ? 1 : n, who, &b)) return rc;
+    return launch_overlap<T>(*b, self, d_bboxes, n_boxes, d_queries6, self ? b->prim_count : n, flags, d_counts, d_offsets, d_list_prims, d_counters,
+                             static_cast<hipStream_t>(stream));
 }
 
 // bvhXX_intersect_ray{,_any}{,_robust} (c_api/bvh.h:277-295 over bvh_impl.h:235-250): one ray, the leaves go to the caller's
@@ -771,7 +783,13 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
         return knn<T>(b, LEAF_TRIANGLE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }        \
     int bvh##S##_knn_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned k, unsigned flags, uint32_t* out_prims, \
                             T* out_dist, uint32_t* counts, bvh_amd_counters* cnt, void* s) {                        \
-        return knn<T>(b, LEAF_SPHERE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }
+        return knn<T>(b, LEAF_SPHERE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }                \
+    int bvh##S##_overlap_boxes(const bvh##S* b, const T* bboxes, size_t n_boxes, const T* queries6, size_t n, unsigned flags, uint32_t* counts, \
+                               const uint64_t* offsets, uint32_t* list_prims, bvh_amd_counters* cnt, void* s) {          \
+        return overlap<T>(b, false, bboxes, n_boxes, queries6, n, flags, counts, offsets, list_prims, cnt, s); }        \
+    int bvh##S##_overlap_self(const bvh##S* b, const T* bboxes, size_t n_boxes, unsigned flags, uint32_t* counts,        \
+                              const uint64_t* offsets, uint32_t* list_prims, bvh_amd_counters* cnt, void* s) {           \
+        return overlap<T>(b, true, bboxes, n_boxes, nullptr, 0, flags, counts, offsets, list_prims, cnt, s); }
 
 #define BVH_AMD_IMPL_RAY(T, D, S, CB, VIS)                                                                          \
     void bvh##S##_intersect_ray(const bvh##S* b, const bvh_ray##S* r, const CB* cb) { intersect_ray_legacy<T, D>(impl<T, D>(b), r, cb, 0u); } \

@@ -116,7 +116,9 @@ struct BvhImpl {
     mutable std::mutex root_mutex;
     int wait_refit() const;
     int note_refit(hipStream_t stream);        // queues the root copy + event (creates both on first use)
-    long long max_prim_id = -1;                // largest value in d_prim_ids (-1: not computed yet; reset when the tree is re-laid out)
+    // largest value in d_prim_ids (-1: not computed yet; reset when the tree is re-laid out). Filled by whoever needs it first, the const
+    // overlap queries included: concurrent fillers store the same value.
+    mutable std::atomic<long long> max_prim_id{-1};
     // device copy
     int device = -1;
     PairNode<T>* d_pairs = nullptr;            // (node_count - 1) / 2 records
@@ -270,6 +272,12 @@ int launch_radius(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T*
                   const uint64_t* d_offsets, uint32_t* d_list_prims, T* d_list_dist, bvh_amd_counters* d_counters, hipStream_t stream);
 // d_offsets[0..n] = {0, c0, c0 + c1, ...}: 64-bit sums, entirely in stream order (no read-back)
 int offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets, hipStream_t stream);
+// overlap.hip: batched box-overlap queries, n x {min.xyz, max.xyz} against d_bboxes[prim_ids[i]] (n_boxes boxes by original id), output as
+// launch_radius without distances (flags: ORIGINAL_IDS, SORTED, UNSORTED); self: the queries are the tree's own primitives, d_queries6
+// is unused, n = prim_count, primitive q lists only i > q (flags: ORIGINAL_IDS)
+template <typename T>
+int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_boxes, const T* d_queries6, size_t n, unsigned flags, uint32_t* d_counts,
+                   const uint64_t* d_offsets, uint32_t* d_list_prims, bvh_amd_counters* d_counters, hipStream_t stream);
 // knn.hip: batched k-nearest queries, n x {x, y, z, max_distance} -> per query a row of k {index, distance} slots in ascending
 // (distance^2, index) order, padded with {INVALID, max_distance} (flags: ORIGINAL_IDS, SORTED, UNSORTED)
 template <typename T>

@@ -44,7 +44,9 @@ int point_query_check(const BvhImpl<T>& b, size_t n, unsigned flags, bool requir
 // per stack entry: a node word and whatever the kind keeps beside it; launches are cut to whole blocks of `lanes`), sorts the batch
 // when asked to or, left to itself, from sort_min queries on, and calls launch(args, deep_d2) for every slice: args holds what the
 // kinds share, deep_d2 the spill's other array (entry - 4 bytes per entry; null for a shallow tree). Owns the scratch behind both.
-template <typename T, typename Launch>
+// Boxes (overlap.hip): a query is a box of 6 scalars, ordered by the cell of its centre; d_queries may then be null when the batch is
+// not reordered (self mode: the lanes take their boxes from d_prims).
+template <typename T, bool Boxes = false, typename Launch>
 int point_query_run(const BvhImpl<T>& b, const T* d_prims, const T* d_queries, size_t n, unsigned flags, bvh_amd_counters* d_counters, size_t entry,
                     size_t lanes, size_t sort_min, int key_bits, const char* who, hipStream_t stream, Launch launch) {
     StreamScope scope(stream);
@@ -81,7 +83,7 @@ int point_query_run(const BvhImpl<T>& b, const T* d_prims, const T* d_queries, s
 
     const bool reorder = n < (size_t{1} << 31) && ((flags & BVH_AMD_RAY_SORTED) ? n > 1 : (flags & BVH_AMD_RAY_UNSORTED) ? false : n >= sort_min);
     if (reorder) {
-        const int rc = query_order<T>(b, d_queries, n, key_bits, who, stream, &sort_mem, &sort_tag, &a.order);
+        const int rc = query_order<T, Boxes>(b, d_queries, n, key_bits, who, stream, &sort_mem, &sort_tag, &a.order);
         if (rc) return release(rc);
     }
 

@@ -37,10 +37,35 @@ __global__ void __launch_bounds__(1024) closest_keys_kernel(const T* queries, ui
     if (threadIdx.x < 256) hist[size_t{threadIdx.x} * tiles + blockIdx.x] = h[threadIdx.x];
 }
 
+// The same keys for query BOXES {min.xyz, max.xyz} (overlap.hip): the cell of the box's centre. A centre that is NaN (a NaN component,
+// -inf + inf) lands in cell 0; the order never changes a result.
+template <typename T>
+__global__ void __launch_bounds__(1024) box_keys_kernel(const T* boxes, uint32_t n, T lx, T ly, T lz, T sx, T sy, T sz, uint32_t cells,
+                                                        uint32_t* keys, uint32_t* hist, uint32_t tiles) {
+    __shared__ uint32_t h[256];
+    if (threadIdx.x < 256) h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t base = blockIdx.x * uint32_t(kRadixTileU32);
+#pragma unroll
+    for (int s0 = 0; s0 < kRadixTileU32 / 1024; ++s0) {
+        const uint32_t i = base + uint32_t(s0) * 1024u + threadIdx.x;
+        if (i < n) {
+            const T* q = boxes + 6ull * i;
+            const T r[8] = { T(0.5) * q[0] + T(0.5) * q[3], T(0.5) * q[1] + T(0.5) * q[4], T(0.5) * q[2] + T(0.5) * q[5], T(0), T(0), T(0), T(0), T(0) };
+            const int hilbert_bits = 31 - __clz(cells);
+            const uint32_t key = ray_key<T>(r, lx, ly, lz, sx, sy, sz, cells, hilbert_bits, 0, T(0));
+            keys[i] = key;
+            atomicAdd(&h[key & 0xFFu], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 256) hist[size_t{threadIdx.x} * tiles + blockIdx.x] = h[threadIdx.x];
+}
+
 // *order = slot -> query index of the n < 2^31 queries sorted by their cell (2^cell_bits cells per axis), in stream order. The scratch
 // behind it is *sort_mem / *sort_tag: the caller hands it to scratch_free once its launches are queued (also when this fails: then
-// *sort_mem may or may not be set). `who` names the caller in error messages.
-template <typename T>
+// *sort_mem may or may not be set). `who` names the caller in error messages. Boxes: d_queries holds 6 scalars per query (box_keys_kernel).
+template <typename T, bool Boxes = false>
 int query_order(const BvhImpl<T>& b, const T* d_queries, size_t n, int cell_bits, const char* who, hipStream_t stream, void** sort_mem,
                 ScratchTag* sort_tag, const uint32_t** order_out) {
     const uint32_t n32 = static_cast<uint32_t>(n);
@@ -57,8 +82,12 @@ int query_order(const BvhImpl<T>& b, const T* d_queries, size_t n, int cell_bits
         sc[k] = ext > T(0) ? T(cells) / ext : T(0);
     }
     const uint32_t tiles = (n32 + kRadixTileU32 - 1) / kRadixTileU32;
-    hipLaunchKernelGGL(closest_keys_kernel<T>, dim3(tiles), dim3(1024), 0, stream, d_queries, n32, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], cells,
-                       keys, hist, tiles);
+    if constexpr (Boxes)
+        hipLaunchKernelGGL(box_keys_kernel<T>, dim3(tiles), dim3(1024), 0, stream, d_queries, n32, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], cells,
+                           keys, hist, tiles);
+    else
+        hipLaunchKernelGGL(closest_keys_kernel<T>, dim3(tiles), dim3(1024), 0, stream, d_queries, n32, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], cells,
+                           keys, hist, tiles);
     BVH_HIP_TRY(hipGetLastError(), BVH_AMD_ERR_HIP);
     uint32_t* order = nullptr;
     const int rc = radix_sort_pairs<uint32_t>(keys, vals, kt, vt, n32, 1, 3 * cell_bits + 3, stream, hist, /*iota_vals=*/true, /*keys_wanted=*/false, &order,

@@ -322,6 +322,8 @@ template <> struct Api<float, 3> {
     static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
+    static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_boxes(h, static_cast<const float*>(bb), nb, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
+    static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_self(h, static_cast<const float*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, float*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitorf v{ user, leaf, inner };
         return bvh3f_intersect_ray_visit(h, static_cast<const bvh_ray3f*>(ray), start, f, &v);
@@ -360,6 +362,8 @@ template <> struct Api<double, 3> {
     static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
+    static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_boxes(h, static_cast<const double*>(bb), nb, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
+    static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_self(h, static_cast<const double*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, double*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitord v{ user, leaf, inner };
         return bvh3d_intersect_ray_visit(h, static_cast<const bvh_ray3d*>(ray), start, f, &v);
@@ -972,6 +976,74 @@ void radius_search_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename
                          std::vector<typename Node::Scalar>* list_dist = nullptr) {
     using T = typename Node::Scalar;
     detail::radius_host<T>(&Api<T, 3>::radius_sphere, bvh.device(), spheres.data(), queries, offsets, list_prims, list_dist, "radius_search_sphere");
+}
+
+// For each query box, every primitive whose box overlaps it (include/bvh_amd.h: bvh3X_overlap_boxes), in the order the tree fixes;
+// closed intervals, exact for a tree built from or refitted to `bboxes`. `bboxes` is indexed by ORIGINAL primitive id, like
+// refit_boxes' (the kind of primitive does not matter). Device form: any of the outputs may be null, as in the C ABI - `counts`
+// (queries.size() entries: untruncated list lengths), `offsets` (queries.size() + 1 entries; null = count pass) with `list_prims`
+// (BVH-order indices, or original ids with BVH_AMD_RAY_ORIGINAL_IDS in `flags`; invalid in the unused rest of a segment).
+// overlap_self_batch: the queries are the tree's own primitives (bvh.prim_ids.size() of them), row q lists only i > q, so the CSR
+// (offsets, list) is the list of unordered overlapping pairs, each once. Exact primitive-against-box tests are the caller's.
+namespace detail {
+template <typename Call>
+void overlap_device(Call call, size_t n, DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims, const char* what) {
+    if ((counts && counts->size() < n) || (offsets && offsets->size() < n + 1)) throw Error(std::string(what) + ": counts need n entries, offsets n + 1");
+    check(call(counts ? counts->data() : nullptr, offsets ? offsets->data() : nullptr, list_prims ? list_prims->data() : nullptr), what);
+}
+// count, offsets on the device, one read of offsets[n] to size the lists, fill
+template <typename Call>
+void overlap_host(Call call, size_t n, std::vector<uint64_t>& offsets, std::vector<uint32_t>& list_prims, const char* what) {
+    offsets.assign(n + 1, 0);
+    list_prims.clear();
+    if (n == 0) return;
+    DeviceArray<uint32_t> d_counts(n);
+    DeviceArray<uint64_t> d_offsets(n + 1);
+    overlap_device(call, n, &d_counts, nullptr, nullptr, what);
+    check(bvh_amd_offsets_from_counts(d_counts.data(), n, d_offsets.data(), nullptr), "offsets_from_counts");
+    d_offsets.download(std::span<uint64_t>(offsets));
+    const size_t total = static_cast<size_t>(offsets[n]);
+    list_prims.resize(total);
+    if (total == 0) return;
+    DeviceArray<uint32_t> d_list(total);
+    overlap_device(call, n, nullptr, &d_offsets, &d_list, what);
+    d_list.download(std::span<uint32_t>(list_prims));
+}
+} // namespace detail
+
+template <typename Node>
+void overlap_boxes_batch(const Bvh<Node>& bvh, const DeviceArray<BBox<typename Node::Scalar, 3>>& bboxes, const DeviceArray<BBox<typename Node::Scalar, 3>>& queries,
+                         DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "overlap queries: 3D trees only");
+    detail::overlap_device([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
+        return Api<T, 3>::overlap_boxes(bvh.device(), bboxes.data(), bboxes.size(), queries.data(), queries.size(), flags, c, o, l); }, queries.size(), counts, offsets, list_prims, "overlap_boxes");
+}
+// Host form: exact lists. Query q's primitives are list_prims[offsets[q] .. offsets[q + 1]).
+template <typename Node>
+void overlap_boxes_batch(const Bvh<Node>& bvh, const DeviceArray<BBox<typename Node::Scalar, 3>>& bboxes, std::span<const BBox<typename Node::Scalar, 3>> queries,
+                         std::vector<uint64_t>& offsets, std::vector<uint32_t>& list_prims, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "overlap queries: 3D trees only");
+    DeviceArray<BBox<T, 3>> d_queries(queries);
+    detail::overlap_host([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
+        return Api<T, 3>::overlap_boxes(bvh.device(), bboxes.data(), bboxes.size(), d_queries.data(), queries.size(), flags, c, o, l); }, queries.size(), offsets, list_prims, "overlap_boxes");
+}
+template <typename Node>
+void overlap_self_batch(const Bvh<Node>& bvh, const DeviceArray<BBox<typename Node::Scalar, 3>>& bboxes, DeviceArray<uint32_t>* counts,
+                        const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "overlap queries: 3D trees only");
+    detail::overlap_device([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
+        return Api<T, 3>::overlap_self(bvh.device(), bboxes.data(), bboxes.size(), flags, c, o, l); }, bvh.prim_ids.size(), counts, offsets, list_prims, "overlap_self");
+}
+template <typename Node>
+void overlap_self_batch(const Bvh<Node>& bvh, const DeviceArray<BBox<typename Node::Scalar, 3>>& bboxes, std::vector<uint64_t>& offsets,
+                        std::vector<uint32_t>& list_prims, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "overlap queries: 3D trees only");
+    detail::overlap_host([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
+        return Api<T, 3>::overlap_self(bvh.device(), bboxes.data(), bboxes.size(), flags, c, o, l); }, bvh.prim_ids.size(), offsets, list_prims, "overlap_self");
 }
 
 // For each query, the k nearest primitives within its max_distance (include/bvh_amd.h: bvhXX_knn_*), k in [1, BVH_AMD_KNN_MAX_K]: row q

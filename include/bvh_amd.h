@@ -571,6 +571,47 @@ BVH_AMD_API int bvh3f_knn_sphere(const struct bvh3f*, const float* d_sph4, const
 BVH_AMD_API int bvh3d_knn_sphere(const struct bvh3d*, const double* d_sph4, const double* d_queries4, size_t n, unsigned k, unsigned flags,
     uint32_t* d_out_prims, double* d_out_dist, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
 
+/* ---- batched box-overlap queries and self-overlap pairs (broad phase) ------------------------------------------------------------ */
+/* d_bboxes is the array bvhXX_build_device and bvhXX_refit_boxes take: n_boxes x {min.xyz, max.xyz}, indexed by ORIGINAL primitive
+ * id; the box of BVH-order primitive i is d_bboxes[prim_ids[i]], so the kind of primitive the tree was built over does not matter.
+ * n_boxes must exceed the largest prim id. d_queries6 is n x {min.xyz, max.xyz} in the same layout.
+ *   test:    closed intervals: boxes a and b overlap iff on every axis a.min <= b.max && b.min <= a.max. Touching boxes overlap, -0
+ *            equals +0, a zero-extent box is a point and overlaps what contains it. A NaN component, or min > max, in the query or in
+ *            a primitive's box makes every comparison that involves it false: an empty list, or a primitive that is never listed.
+ *            The same expression decides whether a child is entered (its box against the query) and whether a primitive is listed.
+ *   result:  every BVH-order index i whose box overlaps the query and all of whose ancestors' boxes overlap it. For a tree fitted to
+ *            these boxes (built from them, or bvhXX_refit_boxes with them: every ancestor box is the min / max union of the boxes
+ *            below it) that is EXACTLY the brute-force set. For boxes the tree was not fitted to it is the walk's set.
+ *   order:   that of bvhXX_radius_search_*: depth-first, left child before right, ascending index inside a leaf; nothing is pruned.
+ *   output:  that of bvhXX_radius_search_* without distances: d_counts[q] is never truncated; query q owns [d_offsets[q],
+ *            d_offsets[q + 1]) of d_list_prims (required iff d_offsets); the first min(count, segment length) entries are written, the
+ *            rest of the segment is padded with BVH_AMD_INVALID, nothing outside a segment is written and a non-ascending segment is
+ *            empty. At least one of d_counts and d_offsets must be given. Count pass, bvh_amd_offsets_from_counts, fill pass = exact
+ *            CSR lists; k fixed slots per query take one pass.
+ *   self:    bvh3X_overlap_self takes no queries: n = bvhXX_get_prim_count, query q IS BVH-order primitive q with the box
+ *            d_bboxes[prim_ids[q]], and its list holds only i > q (compared in BVH order): every unordered overlapping pair appears
+ *            exactly once and no primitive pairs with itself. The CSR (offsets, list) is the pair list; row q stands for primitive q,
+ *            or prim_ids[q] for a caller who uses original ids. Self mode never reorders (BVH order is the tree's spatial order):
+ *            BVH_AMD_RAY_SORTED and BVH_AMD_RAY_UNSORTED are refused there.
+ *   flags:   BVH_AMD_RAY_ORIGINAL_IDS lists prim_ids[i] (the order and the i > q filter stay BVH-order). For bvh3X_overlap_boxes,
+ *            BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED: the reordering key is the Hilbert cell of the query box's centre in the root
+ *            box (with neither, batches of >= 1M queries are reordered). Any other bit: BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * Outputs are in caller order. A query's result does not depend on batch size, position, order, flags, stream or thread. d_counters
+ * (optional) receives {pair records fetched, primitive boxes tested, leaves visited}. Alignment: d_bboxes and d_queries6 to their
+ * scalar, d_offsets and d_counters 8 bytes, d_counts and d_list_prims 4. Refused with BVH_AMD_ERR_ARG: a 2D tree, a NULL handle, a NULL
+ * or misaligned pointer, the forbidden output combinations, a tree without a device copy or without device prim ids, n_boxes at or
+ * below the largest prim id. Re-entrant on a const tree (no work slot is claimed); like every reader of the tree, the caller orders
+ * it after a bvhXX_refit_*. Not offered: the 2D families, exact primitive-against-box tests (triangle SAT, sphere against box: that
+ * narrow phase is the caller's), a dual-tree (tree against tree) traversal, a fused single-walk list variant. */
+BVH_AMD_API int bvh3f_overlap_boxes(const struct bvh3f*, const float* d_bboxes, size_t n_boxes, const float* d_queries6, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_overlap_boxes(const struct bvh3d*, const double* d_bboxes, size_t n_boxes, const double* d_queries6, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_overlap_self(const struct bvh3f*, const float* d_bboxes, size_t n_boxes, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_overlap_self(const struct bvh3d*, const double* d_bboxes, size_t n_boxes, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
+
 /* Optional, additive: pays NOW what the first large batch through a fresh tree would pay inside its own call — the tree's depth /
  * expected-visits pass (one read-back) and the first allocation of the ray-reordering scratch for batches of `n_rays_hint` rays (kept
  * in the library's block cache for that stream). A single Bvh::intersect on a fresh Bvh is the reference's normal use (bvh.h:160-182);
