@@ -510,7 +510,10 @@ def intersect(bvh: Bvh, prims, rays, any_hit: bool = False, robust: bool = False
 
 def closest_points(bvh: Bvh, prims, points, max_distance: float = float("inf"), leaf: str = "tri", counters: bool = False, out=None,
                    sort_queries=None, original_ids: bool = False):
-    """For each point, the nearest primitive within max_distance and its distance (bvhXX_closest_points_*). prims are in BVH order
+    """For each point, the nearest primitive within max_distance and its distance (bvhXX_closest_points_*): among the primitives the
+    walk tests, the lowest BVH-order index of those at the smallest computed distance. A subtree whose box is computed farther than the
+    best so far is skipped, so this is the brute force's argmin by (distance, index) exactly when distances are computed exactly, and
+    within rounding of its distance otherwise. prims are in BVH order
     ((n, 12) PrecomputedTri or (n, 4) spheres, as for intersect). points: (n, 3) with the scalar max_distance, or (n, 4) with a
     per-query radius in column 3 (max_distance left at its default). Returns the (n, 4) tensor of hit records (hits_to_numpy views
     it): prim = BVH-order index (bvh.prim_ids[i] with original_ids) or INVALID, t = distance (max_distance on a miss), (u, v) the
@@ -716,7 +719,9 @@ KNN_MAX_K = 64                                  # BVH_AMD_KNN_MAX_K
 
 def knn(bvh: Bvh, prims, points, k: int, max_distance: float = float("inf"), leaf: str = "tri", distances: bool = True,
         original_ids: bool = False, sort_queries=None, counters: bool = False):
-    """For each point, the k nearest primitives within max_distance (bvhXX_knn_*), in ascending (distance, BVH-order index) order. prims
+    """For each point, the k nearest primitives within max_distance (bvhXX_knn_*), in ascending (distance, BVH-order index) order: the
+    k smallest among the primitives the walk tests, which is the brute force's row exactly when distances are computed exactly and
+    within rounding of its distances otherwise (a primitive computed nearer than its own box can hide an equal one). prims
     are in BVH order, as for closest_points; points: (n, 3) with the scalar max_distance, or (n, 4) with a per-query radius in column 3
     (max_distance left at its default). Returns (ids, dist, counts): ids int32 (n, k), BVH-order indices (bvh.prim_ids[i] with
     original_ids); dist (n, k) beside them (None without `distances`); counts int32 (n,), the valid entries of each row. The unused

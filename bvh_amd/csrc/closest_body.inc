@@ -22,8 +22,13 @@ struct ClosestArgs : PointArgs<T> {
 };
 
 // One query, one lane: depth-first walk, nearer child first, the farther one pushed with its box distance^2; a child or popped entry
-// farther than the best primitive so far is dropped. best starts at max_distance^2; among primitives at the same squared distance the
-// lowest BVH-order index wins, whatever the visiting order. Slot `slot` of the launch (query order[slot], or slot itself); `lane`
+// farther than the best primitive so far is dropped. best starts at max_distance^2; among the primitives the walk TESTS, the lowest
+// BVH-order index of those at the smallest computed squared distance wins, whatever the visiting order. A subtree is skipped when
+// its box's computed distance^2 exceeds `best`, so a primitive whose computed distance rounds below its own leaf box's (a sphere's
+// (fl(sqrt(s)) - r)^2 against the box's exact s; a triangle with area) can hide one at an equal or one-ulp-nearer distance in another
+// leaf. The record is the brute force's (argmin by (d2, index)) exactly when the distances are computed exactly, otherwise its distance
+// is within the tolerance of INTEGRATION.md 3b of it (tests/test_query_fuzz_host.py pins both; docs/HISTORY.md has the open item).
+// Slot `slot` of the launch (query order[slot], or slot itself); `lane`
 // indexes the HBM spill (Deep), `tid` the LDS arrays. cnt += {pair records fetched, primitives tested, leaves visited}.
 template <typename T, int Leaf, bool Stats, bool Deep>
 __device__ inline void closest_lane(const ClosestArgs<T>& a, unsigned long long slot, uint32_t* lds_node, T* lds_d2, int tid,

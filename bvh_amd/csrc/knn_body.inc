@@ -1,6 +1,9 @@
 // Per-lane body of the batched k-nearest query (knn.hip): the k BVH-order primitives — PrecomputedTri or Sphere — nearest to a query
-// point within max_distance, as a row of k {index, distance} slots in ascending (squared distance, index) order. The distance
-// functions are point_walk.inc's (tri_dist2 / sphere_dist2 / box_dist2), so a distance is exactly what closest_points
+// point within max_distance, as a row of k {index, distance} slots in ascending (squared distance, index) order: the k smallest
+// (d2, index) among the primitives the walk TESTS. Those are all of the scene's when the distances are computed exactly; with rounded
+// distances a primitive computed nearer than its own leaf box can hide an equal or one-ulp-nearer one in a skipped subtree, and the
+// row's distances then differ from the brute force's by rounding only (closest_body.inc; docs/HISTORY.md has the open item).
+// The distance functions are point_walk.inc's (tri_dist2 / sphere_dist2 / box_dist2), so a distance is exactly what closest_points
 // measures, and the walk is closest_lane's with the best distance replaced by the worst of the k held: k = 1 gives closest_points'
 // primitive, distance and counters. Kept as an include so that tests/cpp/knn_body_host.cpp compiles the very same text for the host
 // (one emulated lane per query). Expects what point_walk.inc expects.
@@ -81,8 +84,9 @@ __device__ inline void knn_make_heap(T* cand_d2, uint32_t* cand_id, uint32_t str
 
 // One query, one lane: closest_lane's walk — depth-first, nearer child first (ties left), the farther one pushed with its box
 // distance^2 — pruned against `worst`: max_distance^2 until k candidates are held, then the d2 of the largest (d2, index) held. A
-// child or a popped entry is kept iff its box distance^2 <= worst (not <: a primitive at the same distance with a lower index must
-// stay reachable). Inside a leaf the index ascends; a primitive is accepted while fewer than k are held iff d2 <= max_distance^2,
+// child or a popped entry is kept iff its box distance^2 <= worst (not <: a primitive at the same distance with a lower index
+// stays reachable wherever its box is not computed farther than `worst`). Inside a leaf the index ascends; a primitive is accepted
+// while fewer than k are held iff d2 <= max_distance^2,
 // afterwards iff (d2, index) is below the largest held, which it replaces. The candidates are appended unordered until the k-th
 // makes them a max-heap; a replacement is one sift-down; at the end an in-place heapsort leaves them ascending, and the row is
 // written: nothing is stored while walking, so an invalid query still pads its row. Slot `slot` of the launch (query order[slot], or

@@ -1047,7 +1047,8 @@ void overlap_self_batch(const Bvh<Node>& bvh, const DeviceArray<BBox<typename No
 }
 
 // For each query, the k nearest primitives within its max_distance (include/bvh_amd.h: bvhXX_knn_*), k in [1, BVH_AMD_KNN_MAX_K]: row q
-// is out_prims[q * k .. q * k + k), BVH-order indices in ascending (distance, index) order, the unused slots invalid; `out_dist`
+// is out_prims[q * k .. q * k + k), BVH-order indices in ascending (distance, index) order among the primitives the walk tests (the brute
+// force's row when distances are computed exactly, within rounding of it otherwise), the unused slots invalid; `out_dist`
 // (optional) the distances beside them (max_distance in the unused slots); `counts` (optional) the valid entries of each row.
 namespace detail {
 template <typename T>

@@ -485,7 +485,10 @@ BVH_AMD_API int bvh3d_intersect_rays_sphere(const struct bvh3d*, const double* d
 /* d_queries4 holds n x {x, y, z, max_distance} of the tree's scalar type (16 B per query for 3f, 32 B for 3d); d_prims are the
  * BVH-order PrecomputedTri (tri) or Sphere<T, 3> {c, r} (sphere) arrays that bvhXX_intersect_rays_* take. One record per query:
  *   hit:  prim = the BVH-order index (bvh.prim_ids[i] with BVH_AMD_RAY_ORIGINAL_IDS) of the primitive at the smallest squared
- *         distance <= max_distance^2, ties to the lowest index; t = sqrt(d^2). Triangles: distance to the solid triangle, (u, v) the
+ *         distance <= max_distance^2 among the primitives the walk tests, ties among those to the lowest index; t = sqrt(d^2). A
+ *         subtree is skipped when its box's computed squared distance exceeds the best so far, so a primitive whose computed distance
+ *         rounds below its box's can hide one at an equal or one-ulp-nearer distance: the record is the brute force's argmin by
+ *         (d2, index) exactly when the distances are computed exactly, and its distance is within rounding of it otherwise. Triangles: distance to the solid triangle, (u, v) the
  *         barycentrics of its closest point, point = p0 + u (p1 - p0) + v (p2 - p0). Spheres: max(|q - c| - r, 0), u = v = 0.
  *   miss: prim = BVH_AMD_INVALID, t = max_distance, u = v = 0 (also for a NaN coordinate and a negative or NaN max_distance;
  *         +inf = unbounded).
@@ -545,7 +548,10 @@ BVH_AMD_API int bvh_amd_offsets_from_counts(const uint32_t* d_counts, size_t n, 
  * [1, BVH_AMD_KNN_MAX_K]. With r2 = max_distance * max_distance (rounded in the scalar type), the result of a query is the k smallest
  * pairs (d2, i), in lexicographic order, among the BVH-order indices i with d2(i) <= r2; d2 is the squared distance
  * bvhXX_closest_points_* measures. The pairs are listed in ascending (d2, i) order: equal squared distances by ascending BVH-order
- * index (also when BVH_AMD_RAY_ORIGINAL_IDS maps the reported ids). k = 1 is closest_points' {prim, t}.
+ * index (also when BVH_AMD_RAY_ORIGINAL_IDS maps the reported ids). k = 1 is closest_points' {prim, t}. As there, "smallest" is among
+ * the primitives the walk tests: that is the whole scene, and the row the brute force's, when the distances are computed exactly; with
+ * rounded distances a primitive computed nearer than its own box can hide an equal or one-ulp-nearer one in a skipped subtree, and
+ * the row's distances differ from the brute force's by rounding only.
  *   output:  d_out_prims (n x k, row-major, caller order, required): BVH-order indices (bvh.prim_ids[i] with
  *            BVH_AMD_RAY_ORIGINAL_IDS). d_out_dist (n x k, or NULL): sqrt(d2), correctly rounded. d_counts (n, or NULL): the valid
  *            entries of each row, <= k. The unused slots of a row hold {BVH_AMD_INVALID, max_distance} (the miss record of
