@@ -606,16 +606,23 @@ def radius_search(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", max_p
         -1 (INVALID) and the query's radius; returns (offsets, ids, dist, counts), counts (int32, untruncated) telling which lists
         overflowed.
     With counters, (pairs, tests, leaves) of the pass that wrote the lists is appended to the result."""
-    torch = _torch()
     q, p, dt = _point_query_args(bvh, prims, points, radius, leaf, "radius_search")
     n = q.shape[0]
-    dev = q.device
     fn = getattr(_lib.load(), f"bvh{bvh._s}_radius_search_{leaf}")
     flags = int(_sort_flags(sort_queries, original_ids))
+    call = lambda counts, offsets, ids, dist, cnt: fn(bvh._h, p.data_ptr(), q.data_ptr(), n, flags, counts, offsets, ids, dist, cnt, _stream())
+    return _two_pass_lists("radius_search", call, n, q.device, max_per_query, counters, dt if distances else None)
+
+
+def _two_pass_lists(who: str, call, n: int, dev, max_per_query, counters: bool, dist_dtype=None):
+    """Count pass, offsets, fill pass (or one pass into max_per_query slots) of call(counts, offsets, ids, dist, counters), the list
+    output of radius_search and the overlap queries: (offsets, ids, dist[, counts][, counters]); dist (None without dist_dtype) is
+    written beside ids."""
+    torch = _torch()
     cnt = torch.zeros(3, dtype=torch.int64, device=dev) if counters else None
     counts = torch.zeros(n, dtype=torch.int32, device=dev)
     if max_per_query is None:
-        _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, flags, counts.data_ptr(), None, None, None, None, _stream()), "radius_search")
+        _lib.check(call(counts.data_ptr(), None, None, None, None), who)
         offsets = offsets_from_counts(counts)
         total = int(offsets[-1].item())
     else:
@@ -625,10 +632,10 @@ def radius_search(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", max_p
         offsets = torch.arange(n + 1, dtype=torch.int64, device=dev) * k
         total = n * k
     ids = torch.empty(max(total, 1), dtype=torch.int32, device=dev)               # (never a null pointer: an empty result is still a list)
-    dist = torch.empty(max(total, 1), dtype=dt, device=dev) if distances else None
-    _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, flags, counts.data_ptr() if max_per_query is not None else None, offsets.data_ptr(), ids.data_ptr(),
-                  dist.data_ptr() if distances else None, cnt.data_ptr() if counters else None, _stream()), "radius_search")
-    ids, dist = ids[:total], dist[:total] if distances else None
+    dist = torch.empty(max(total, 1), dtype=dist_dtype, device=dev) if dist_dtype is not None else None
+    _lib.check(call(counts.data_ptr() if max_per_query is not None else None, offsets.data_ptr(), ids.data_ptr(),
+                    dist.data_ptr() if dist is not None else None, cnt.data_ptr() if counters else None), who)
+    ids, dist = ids[:total], dist[:total] if dist is not None else None
     out = (offsets, ids, dist) if max_per_query is None else (offsets, ids, dist, counts)
     return out + (cnt,) if counters else out
 
@@ -657,27 +664,6 @@ def overlap_count(bvh: Bvh, bboxes, query_boxes, sort_queries=None, counters: bo
     return (counts, cnt) if counters else counts
 
 
-def _overlap_lists(bvh: Bvh, who: str, call, n: int, dev, max_per_query, counters: bool):
-    """Count pass, offsets, fill pass (or one pass into max_per_query slots) of call(counts, offsets, ids, counters)."""
-    torch = _torch()
-    cnt = torch.zeros(3, dtype=torch.int64, device=dev) if counters else None
-    counts = torch.zeros(n, dtype=torch.int32, device=dev)
-    if max_per_query is None:
-        _lib.check(call(counts.data_ptr(), None, None, None), who)
-        offsets = offsets_from_counts(counts)
-        total = int(offsets[-1].item())
-    else:
-        k = int(max_per_query)
-        if k < 0:
-            raise ValueError("max_per_query must not be negative")
-        offsets = torch.arange(n + 1, dtype=torch.int64, device=dev) * k
-        total = n * k
-    ids = torch.empty(max(total, 1), dtype=torch.int32, device=dev)               # (never a null pointer: an empty result is still a list)
-    _lib.check(call(counts.data_ptr() if max_per_query is not None else None, offsets.data_ptr(), ids.data_ptr(), cnt.data_ptr() if counters else None), who)
-    out = (offsets, ids[:total]) if max_per_query is None else (offsets, ids[:total], counts)
-    return out + (cnt,) if counters else out
-
-
 def overlap_search(bvh: Bvh, bboxes, query_boxes, max_per_query=None, original_ids: bool = False, sort_queries=None, counters: bool = False):
     """For each query box, the primitives whose boxes overlap it (bvh3X_overlap_boxes), in the order the tree fixes (depth-first, left
     child first, ascending index inside a leaf). For a tree built from or refitted to `bboxes` this is exactly the brute-force set.
@@ -691,8 +677,9 @@ def overlap_search(bvh: Bvh, bboxes, query_boxes, max_per_query=None, original_i
     fn = getattr(_lib.load(), f"bvh{bvh._s}_overlap_boxes")
     flags = int(_sort_flags(sort_queries, original_ids))
     n = q.shape[0]
-    call = lambda counts, offsets, ids, cnt: fn(bvh._h, bb.data_ptr(), bb.shape[0], q.data_ptr(), n, flags, counts, offsets, ids, cnt, _stream())
-    return _overlap_lists(bvh, "overlap_search", call, n, q.device, max_per_query, counters)
+    call = lambda counts, offsets, ids, _, cnt: fn(bvh._h, bb.data_ptr(), bb.shape[0], q.data_ptr(), n, flags, counts, offsets, ids, cnt, _stream())
+    out = _two_pass_lists("overlap_search", call, n, q.device, max_per_query, counters)
+    return out[:2] + out[3:]                                                        # (no distances)
 
 
 def self_overlaps(bvh: Bvh, bboxes, original_ids: bool = True, counters: bool = False):
@@ -704,14 +691,14 @@ def self_overlaps(bvh: Bvh, bboxes, original_ids: bool = True, counters: bool = 
     bb, _ = _overlap_args(bvh, bboxes, None, "self_overlaps")
     fn = getattr(_lib.load(), f"bvh{bvh._s}_overlap_self")
     n = bvh.prim_count
-    call = lambda counts, offsets, ids, cnt: fn(bvh._h, bb.data_ptr(), bb.shape[0], 8 if original_ids else 0, counts, offsets, ids, cnt, _stream())
-    out = _overlap_lists(bvh, "self_overlaps", call, n, bb.device, None, counters)
+    call = lambda counts, offsets, ids, _, cnt: fn(bvh._h, bb.data_ptr(), bb.shape[0], 8 if original_ids else 0, counts, offsets, ids, cnt, _stream())
+    out = _two_pass_lists("self_overlaps", call, n, bb.device, None, counters)
     offsets, ids = out[0], out[1]
     rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=bb.device), offsets[1:] - offsets[:-1])
     if original_ids:
         rows = bvh.device_prim_ids().long()[rows]
     pairs = torch.stack([rows, ids.long()], dim=1)
-    return (pairs, out[2]) if counters else pairs
+    return (pairs, out[3]) if counters else pairs
 
 
 KNN_MAX_K = 64                                  # BVH_AMD_KNN_MAX_K

@@ -1,8 +1,9 @@
 // Batched box-overlap queries for gfx950: for every query box {min.xyz, max.xyz}, how many BVH-order primitives have a box that
 // overlaps it (closed intervals) and, optionally, which ones; and the self-overlap pairs of a tree's own primitives (the broad phase of
 // a collision test). The primitives' boxes are the caller's array indexed by original primitive id, the one bvhXX_build_device and
-// bvhXX_refit_boxes take, read through the tree's prim ids. The per-lane walk is overlap_body.inc (shared with the host test harness,
-// tests/cpp/overlap_body_host.cpp) over point_walk.inc (stack, streaming stores); the launch path is point_query.h's.
+// bvhXX_refit_boxes take, read through the tree's prim ids. The per-lane body is overlap_body.inc (shared with the host test harness,
+// tests/cpp/overlap_body_host.cpp): the query box and its tests, handed to the walk radius.hip uses too, list_walk.inc (stack,
+// descent, counts, segments), over point_walk.inc (stack tiers, streaming stores); the launch path is point_query.h's.
 //
 // MI355X mapping (radius.hip's, with the overlap test in place of the distance to a box):
 //   * one lane per query, one-shot grid of ceil(n / 256) blocks: no ticket counter, so no work slot of the tree is claimed and any
@@ -48,11 +49,8 @@ int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_b
         return fail(BVH_AMD_ERR_ARG, std::string(who) + ": unsupported flags (ORIGINAL_IDS only: self mode walks in BVH order and never reorders)");
     const bool aligned = !(misaligned(d_bboxes, sizeof(T)) || misaligned(d_queries6, sizeof(T)) || misaligned(d_offsets, 8) || misaligned(d_counters, 8) ||
                            misaligned(d_counts, 4) || misaligned(d_list_prims, 4));
-    const char* fault = !d_counts && !d_offsets     ? "at least one of d_counts and d_offsets is required"
-                        : d_offsets && !d_list_prims ? "d_offsets needs d_list_prims"
-                        : !d_offsets && d_list_prims ? "lists need d_offsets"
-                        : !aligned ? "device pointers must be aligned (boxes and queries to their scalar, offsets and counters 8 bytes, counts and list prims 4)"
-                                   : nullptr;
+    const char* fault = list_output_fault(d_counts, d_offsets, d_list_prims, nullptr);
+    if (!fault && !aligned) fault = "device pointers must be aligned (boxes and queries to their scalar, offsets and counters 8 bytes, counts and list prims 4)";
     if (const int rc = point_query_check(b, n, flags, d_bboxes && (self || d_queries6), fault, who); rc || n == 0) return rc;
     if (!b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH has no device prim ids");
     long long largest = b.max_prim_id.load();
@@ -67,14 +65,11 @@ int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_b
     const unsigned run_flags = self ? flags | BVH_AMD_RAY_UNSORTED : flags;
     return point_query_run<T, true>(b, d_bboxes, d_queries6, n, run_flags, d_counters, sizeof(uint32_t), kBlock, kPointSortMin, kPointKeyBits, who, stream,
                                     [&](const PointArgs<T>& args, T*) {
-        const OverlapArgs<T> a{args, b.d_prim_ids, d_counts, reinterpret_cast<const unsigned long long*>(d_offsets), d_list_prims};
-        auto launch = [&](auto stats, auto deep, auto fill) {
+        const OverlapArgs<T> a{{args, d_counts, reinterpret_cast<const unsigned long long*>(d_offsets), d_list_prims}, b.d_prim_ids};
+        // (the ladder's leaf kind is unused here: a box is a box)
+        return list_query_dispatch(LEAF_TRIANGLE, d_counters != nullptr, a.deep_cap != 0, a.offsets != nullptr, [&](auto, auto stats, auto deep, auto fill) {
             return self ? point_query_launch(overlap_kernel<T, stats(), deep(), fill(), true>, a, kBlock, 0, stream)
                         : point_query_launch(overlap_kernel<T, stats(), deep(), fill(), false>, a, kBlock, 0, stream);
-        };
-        // (the ladder of point_query_dispatch; its leaf kind is unused here: a box is a box)
-        return point_query_dispatch(LEAF_TRIANGLE, d_counters != nullptr, a.deep_cap != 0, [&](auto, auto stats, auto deep) {
-            return a.offsets ? launch(stats, deep, std::true_type{}) : launch(stats, deep, std::false_type{});
         });
     });
 }

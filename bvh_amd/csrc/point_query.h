@@ -1,5 +1,6 @@
-// The launch path of the batched point queries (closest.hip, radius.hip, knn.hip), once: the thresholds, the argument checks the three
-// share, the driver (counters, depth pass, HBM spill, reading order, launches) and the kernels' counter epilogue. Expects common.h,
+// The launch path of the batched point and box queries (closest.hip, radius.hip, knn.hip, overlap.hip), once: the thresholds, the
+// argument checks they share, the driver (counters, depth pass, HBM spill, reading order, launches), the output check and the Fill
+// switch of the two list queries, and the kernels' counter epilogue. Expects common.h,
 // trace_device.h, ray_key.h, query_order.h and the kind's body (point_walk.inc: PointArgs) to have been included.
 #pragma once
 
@@ -105,6 +106,24 @@ int point_query_dispatch(int leaf_kind, bool stats, bool deep, F f) {
     };
     if (deep) return stats ? leaf(std::true_type{}, std::true_type{}) : leaf(std::false_type{}, std::true_type{});
     return stats ? leaf(std::true_type{}, std::false_type{}) : leaf(std::false_type{}, std::false_type{});
+}
+
+// The list queries (radius.hip, overlap.hip) have one more choice: f(leaf, stats, deep, fill), fill = the launch has offsets and
+// writes lists (the kernels <..., Fill = true>).
+template <typename F>
+int list_query_dispatch(int leaf_kind, bool stats, bool deep, bool fill, F f) {
+    return point_query_dispatch(leaf_kind, stats, deep, [&](auto leaf, auto s, auto d) {
+        return fill ? f(leaf, s, d, std::true_type{}) : f(leaf, s, d, std::false_type{});
+    });
+}
+
+// What is wrong with the output pointers of a list query, or null: `fault` of point_query_check, ahead of the kind's own alignment
+// message. list_extra: the kind's other list array (radius search's distances), or null.
+inline const char* list_output_fault(const void* d_counts, const void* d_offsets, const void* d_list_prims, const void* list_extra) {
+    return !d_counts && !d_offsets                     ? "at least one of d_counts and d_offsets is required"
+           : d_offsets && !d_list_prims                ? "d_offsets needs d_list_prims"
+           : !d_offsets && (d_list_prims || list_extra) ? "lists need d_offsets"
+                                                       : nullptr;
 }
 
 template <typename Args>

@@ -1,5 +1,5 @@
-// What the per-lane bodies of the three point queries share (closest_body.inc, radius_body.inc, knn_body.inc): the arguments common to
-// their kernels, the query load, the squared distance of a point to one primitive — a PrecomputedTri {p0, e1 = p0 - p1, e2 = p2 - p0, n}
+// What the per-lane bodies of the point and box queries share (closest_body.inc, knn_body.inc, and through list_walk.inc
+// radius_body.inc and overlap_body.inc): the arguments common to their kernels, the query load, the squared distance of a point to one primitive — a PrecomputedTri {p0, e1 = p0 - p1, e2 = p2 - p0, n}
 // or a Sphere {c, r} — and to a box, the streaming stores of the outputs and the index arithmetic of the walk's three-tier stack. Kept as an
 // include so that the host harnesses (tests/cpp/*_body_host.cpp) compile the very same text, through the bodies, with one emulated lane
 // per query. Expects trace_device.h (Num, dot3, load_pair, load_prim12, load_prim4, kBlock) and common.h, or the harnesses' stand-ins

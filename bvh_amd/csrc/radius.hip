@@ -1,7 +1,8 @@
 // Batched radius queries for gfx950: for every query point {x, y, z, max_distance}, how many BVH-order primitives (PrecomputedTri or
-// Sphere<T, 3>) lie within max_distance of it and, optionally, which ones, at what distance. The per-lane walk is radius_body.inc
-// (shared with the host test harness, tests/cpp/radius_body_host.cpp) over point_walk.inc (distance functions, stack); the launch path
-// is point_query.h's; this file holds the kernel, what is specific to the query, and the offsets scan.
+// Sphere<T, 3>) lie within max_distance of it and, optionally, which ones, at what distance. The per-lane body is radius_body.inc
+// (shared with the host test harness, tests/cpp/radius_body_host.cpp): the query and its tests, handed to the walk of the list
+// queries, list_walk.inc (stack, descent, counts, segments; shared with overlap.hip), over point_walk.inc (distance functions, stack
+// tiers); the launch path is point_query.h's; this file holds the kernel, what is specific to the query, and the offsets scan.
 //
 // MI355X mapping:
 //   * one lane per query, one-shot grid of ceil(n / 256) blocks: no ticket counter, so no work slot of the tree is claimed and any
@@ -128,19 +129,15 @@ int launch_radius(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T*
                   const uint64_t* d_offsets, uint32_t* d_list_prims, T* d_list_dist, bvh_amd_counters* d_counters, hipStream_t stream) {
     const bool aligned = !(misaligned(d_prims, 16) || misaligned(d_queries, 16) || misaligned(d_offsets, 8) || misaligned(d_counters, 8) ||
                            misaligned(d_counts, 4) || misaligned(d_list_prims, 4) || misaligned(d_list_dist, sizeof(T)));
-    const char* fault = !d_counts && !d_offsets                       ? "at least one of d_counts and d_offsets is required"
-                        : d_offsets && !d_list_prims                  ? "d_offsets needs d_list_prims"
-                        : !d_offsets && (d_list_prims || d_list_dist) ? "lists need d_offsets"
-                        : !aligned ? "device pointers must be aligned (prims and queries 16 bytes, offsets and counters 8, "
-                                     "counts, list prims and list distances to their element)"
-                                   : nullptr;
+    const char* fault = list_output_fault(d_counts, d_offsets, d_list_prims, d_list_dist);
+    if (!fault && !aligned) fault = "device pointers must be aligned (prims and queries 16 bytes, offsets and counters 8, "
+                                    "counts, list prims and list distances to their element)";
     if (const int rc = point_query_check(b, n, flags, d_prims && d_queries, fault, "radius_search"); rc || n == 0) return rc;
     return point_query_run<T>(b, d_prims, d_queries, n, flags, d_counters, sizeof(uint32_t), kBlock, kPointSortMin, kPointKeyBits, "radius_search", stream,
                               [&](const PointArgs<T>& args, T*) {
-        const RadiusArgs<T> a{args, d_counts, reinterpret_cast<const unsigned long long*>(d_offsets), d_list_prims, d_list_dist};
-        return point_query_dispatch(leaf_kind, d_counters != nullptr, a.deep_cap != 0, [&](auto leaf, auto stats, auto deep) {
-            return a.offsets ? point_query_launch(radius_kernel<T, leaf(), stats(), deep(), true>, a, kBlock, 0, stream)
-                             : point_query_launch(radius_kernel<T, leaf(), stats(), deep(), false>, a, kBlock, 0, stream);
+        const RadiusArgs<T> a{{args, d_counts, reinterpret_cast<const unsigned long long*>(d_offsets), d_list_prims}, d_list_dist};
+        return list_query_dispatch(leaf_kind, d_counters != nullptr, a.deep_cap != 0, a.offsets != nullptr, [&](auto leaf, auto stats, auto deep, auto fill) {
+            return point_query_launch(radius_kernel<T, leaf(), stats(), deep(), fill()>, a, kBlock, 0, stream);
         });
     });
 }

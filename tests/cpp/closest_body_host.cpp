@@ -30,19 +30,9 @@ int walk(const void* pairs, uint32_t root_index, const void* prims, const void* 
     a.pairs = static_cast<const PairNode<T>*>(pairs); a.prims = static_cast<const T*>(prims); a.queries = static_cast<const T*>(queries);
     a.hits = static_cast<typename HitOf<T>::Type*>(hits); a.n = n; a.first = 0; a.order = order; a.prim_ids = prim_ids; a.counters = nullptr;
     a.deep_cap = deep_cap; a.root_index = root_index;
-    const int nt = std::max(1, threads);
-    std::vector<std::thread> pool;
-    std::vector<unsigned long long> sums(3 * size_t(nt), 0);
-    for (int t = 0; t < nt; ++t) {
-        const unsigned long long b = n * t / nt, e = n * (t + 1) / nt;
-        pool.emplace_back([&, t, b, e] {
-            unsigned long long cnt[3] = {0, 0, 0};
-            if (deep_cap) walk_range<T, Leaf, true>(a, b, e, cnt); else walk_range<T, Leaf, false>(a, b, e, cnt);
-            for (int k = 0; k < 3; ++k) sums[3 * size_t(t) + k] = cnt[k];
-        });
-    }
-    for (auto& th : pool) th.join();
-    for (int k = 0; k < 3; ++k) { counters3[k] = 0; for (int t = 0; t < nt; ++t) counters3[k] += sums[3 * size_t(t) + k]; }
+    run_lanes(n, threads, counters3, [&](unsigned long long b, unsigned long long e, unsigned long long (&cnt)[3]) {
+        if (deep_cap) walk_range<T, Leaf, true>(a, b, e, cnt); else walk_range<T, Leaf, false>(a, b, e, cnt);
+    });
     return 0;
 }
 

@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE (CPU, no GPU): what the host harnesses of the point queries (closest_body_host.cpp, radius_body_host.cpp,
-// knn_body_host.cpp) put in front of the kernels' text: single-lane stand-ins for hip_runtime.h and for bvh_amd/csrc/common.h, then the
-// device helpers of bvh_amd/csrc/trace_device.h. The stand-ins must follow common.h (PairNode, kCountBits, LEAF_*).
+// knn_body_host.cpp, overlap_body_host.cpp) put in front of the kernels' text: single-lane stand-ins for hip_runtime.h and for
+// bvh_amd/csrc/common.h, then the device helpers of bvh_amd/csrc/trace_device.h, and the thread-split scaffold of their walks. The
+// stand-ins must follow common.h (PairNode, kCountBits, LEAF_*).
 #pragma once
 
 #include <algorithm>
@@ -49,3 +50,22 @@ enum { LEAF_TRIANGLE = 0, LEAF_SPHERE = 1 };
 } // namespace bvh_amd
 
 #include "../../bvh_amd/csrc/trace_device.h"
+
+// ---- the scaffold of a harness's walk: slots [0, n) split over `threads` host threads, range(begin, end, cnt) on each (it walks its
+// slots one emulated lane at a time and adds to its own cnt), counters3 = the sum of the threads' cnt -----------------------------------
+template <typename Range>
+void run_lanes(size_t n, int threads, unsigned long long* counters3, Range range) {
+    const int nt = std::max(1, threads);
+    std::vector<std::thread> pool;
+    std::vector<unsigned long long> sums(3 * size_t(nt), 0);
+    for (int t = 0; t < nt; ++t) {
+        const unsigned long long b = n * t / nt, e = n * (t + 1) / nt;
+        pool.emplace_back([&, t, b, e] {
+            unsigned long long cnt[3] = {0, 0, 0};
+            range(b, e, cnt);
+            for (int k = 0; k < 3; ++k) sums[3 * size_t(t) + k] = cnt[k];
+        });
+    }
+    for (auto& th : pool) th.join();
+    for (int k = 0; k < 3; ++k) { counters3[k] = 0; for (int t = 0; t < nt; ++t) counters3[k] += sums[3 * size_t(t) + k]; }
+}

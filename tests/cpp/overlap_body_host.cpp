@@ -1,5 +1,5 @@
-// TEST INFRASTRUCTURE (CPU, no GPU): compiles the text of the box-overlap kernel — bvh_amd/csrc/overlap_body.inc (over point_walk.inc)
-// with the device helpers of bvh_amd/csrc/trace_device.h — for the HOST and runs it with one emulated lane per query (the queries of
+// TEST INFRASTRUCTURE (CPU, no GPU): compiles the text of the box-overlap kernel — bvh_amd/csrc/overlap_body.inc (over list_walk.inc, the
+// walk it shares with the radius query, and point_walk.inc) with the device helpers of bvh_amd/csrc/trace_device.h — for the HOST and runs it with one emulated lane per query (the queries of
 // a batch one after another, or split over host threads). What it can show: the walk of the very source the device runs lists
 // exactly the primitives a numpy brute force over the same closed-interval test lists, in the tree's order, and keeps to its
 // segment; the device's counts, lists and counters must equal these byte for byte. What it cannot show: anything that needs the
@@ -34,20 +34,10 @@ int walk(const void* pairs, uint32_t root_index, const void* bboxes, const uint3
     a.n = n; a.first = 0; a.order = order; a.prim_ids = original_ids ? box_ids : nullptr; a.counters = nullptr;
     a.deep_cap = deep_cap; a.root_index = root_index;
     const bool self = queries == nullptr;
-    const int nt = std::max(1, threads);
-    std::vector<std::thread> pool;
-    std::vector<unsigned long long> sums(3 * size_t(nt), 0);
-    for (int t = 0; t < nt; ++t) {
-        const unsigned long long b = n * t / nt, e = n * (t + 1) / nt;
-        pool.emplace_back([&, t, b, e] {
-            unsigned long long cnt[3] = {0, 0, 0};
-            if (deep_cap) { if (self) walk_range<T, true, true>(a, b, e, cnt); else walk_range<T, true, false>(a, b, e, cnt); }
-            else { if (self) walk_range<T, false, true>(a, b, e, cnt); else walk_range<T, false, false>(a, b, e, cnt); }
-            for (int k = 0; k < 3; ++k) sums[3 * size_t(t) + k] = cnt[k];
-        });
-    }
-    for (auto& th : pool) th.join();
-    for (int k = 0; k < 3; ++k) { counters3[k] = 0; for (int t = 0; t < nt; ++t) counters3[k] += sums[3 * size_t(t) + k]; }
+    run_lanes(n, threads, counters3, [&](unsigned long long b, unsigned long long e, unsigned long long (&cnt)[3]) {
+        if (deep_cap) { if (self) walk_range<T, true, true>(a, b, e, cnt); else walk_range<T, true, false>(a, b, e, cnt); }
+        else { if (self) walk_range<T, false, true>(a, b, e, cnt); else walk_range<T, false, false>(a, b, e, cnt); }
+    });
     return 0;
 }
 

@@ -1,5 +1,5 @@
-// TEST INFRASTRUCTURE (CPU, no GPU): compiles the text of the radius-query kernel — bvh_amd/csrc/radius_body.inc (over point_walk.inc,
-// which has the distance functions) with the device helpers of bvh_amd/csrc/trace_device.h — for the HOST and runs it with
+// TEST INFRASTRUCTURE (CPU, no GPU): compiles the text of the radius-query kernel — bvh_amd/csrc/radius_body.inc (over list_walk.inc, the walk it
+// shares with the overlap query, and point_walk.inc, which has the distance functions) with the device helpers of bvh_amd/csrc/trace_device.h — for the HOST and runs it with
 // one emulated lane per query (the queries of a batch one after another, or split over host threads). What it can show: the walk of
 // the very source the device runs lists the primitives a brute force over the same distance functions lists, in the tree's order, and
 // keeps to its segment; the device's counts, lists and distances must equal these bit for bit. What it cannot show: anything that
@@ -33,19 +33,9 @@ int walk(const void* pairs, uint32_t root_index, const void* prims, const void* 
     a.counts = counts; a.offsets = reinterpret_cast<const unsigned long long*>(offsets); a.list_prims = list_prims; a.list_dist = static_cast<T*>(list_dist);
     a.n = n; a.first = 0; a.order = order; a.prim_ids = prim_ids; a.counters = nullptr;
     a.deep_cap = deep_cap; a.root_index = root_index;
-    const int nt = std::max(1, threads);
-    std::vector<std::thread> pool;
-    std::vector<unsigned long long> sums(3 * size_t(nt), 0);
-    for (int t = 0; t < nt; ++t) {
-        const unsigned long long b = n * t / nt, e = n * (t + 1) / nt;
-        pool.emplace_back([&, t, b, e] {
-            unsigned long long cnt[3] = {0, 0, 0};
-            if (deep_cap) walk_range<T, Leaf, true>(a, b, e, cnt); else walk_range<T, Leaf, false>(a, b, e, cnt);
-            for (int k = 0; k < 3; ++k) sums[3 * size_t(t) + k] = cnt[k];
-        });
-    }
-    for (auto& th : pool) th.join();
-    for (int k = 0; k < 3; ++k) { counters3[k] = 0; for (int t = 0; t < nt; ++t) counters3[k] += sums[3 * size_t(t) + k]; }
+    run_lanes(n, threads, counters3, [&](unsigned long long b, unsigned long long e, unsigned long long (&cnt)[3]) {
+        if (deep_cap) walk_range<T, Leaf, true>(a, b, e, cnt); else walk_range<T, Leaf, false>(a, b, e, cnt);
+    });
     return 0;
 }
 

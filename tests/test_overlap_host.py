@@ -1,4 +1,4 @@
-"""CPU: the TEXT of the box-overlap kernel (bvh_amd/csrc/overlap_body.inc + point_walk.inc + trace_device.h) compiled for the host by
+"""CPU: the TEXT of the box-overlap kernel (bvh_amd/csrc/overlap_body.inc + list_walk.inc + point_walk.inc + trace_device.h) compiled for the host by
 tests/cpp/overlap_body_host.cpp. The walk over the golden trees against a numpy brute force (the closed-interval test in the scene's
 scalar type, mapped to BVH order through prim_ids and listed in the tree's left-first depth-first order): EXACT equality, nothing
 excluded. The shapes of the output (count pass, exact offsets, fixed segments, padding, guard zones); self mode and its pair totals;
@@ -15,12 +15,9 @@ import pytest
 from conftest import ROOT, load_golden, parse_stream
 from test_closest_point_host import GOLDEN_SCENES, chain_tree, scene_queries
 from test_kernel_body_host import _aligned, pair_records
-from test_radius_search_host import dfs_prim_order
+from test_radius_search_host import GUARD, INVALID, SENT_PRIM, _p, dfs_prim_order, guards_intact
 
 HARNESS = os.path.join(ROOT, "tests", "cpp", "overlap_body_host.cpp")
-INVALID = 0xFFFFFFFF
-GUARD = 64                                                     # sentinel entries on either side of a list buffer
-SENT_PRIM = 0xDEADBEEF
 TREES = ["binned", "parallel_high"]
 # numpy, closed intervals, over the scenes' own boxes: unordered overlapping pairs, and how many of them merely touch (they overlap
 # with closed intervals and not with open ones)
@@ -39,10 +36,6 @@ def compile_harness(out_dir):
     dll.overlap_host_walk.restype = I
     dll.overlap_host_walk.argtypes = [I, P, U, P, P, P, Z, P, I, U, I, P, P, P, P]
     return dll
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def prim_boxes(raw):
@@ -139,10 +132,6 @@ def host_walk(dll, tree, queries, offsets=None, total=0, counts=True, order=None
     assert dll.overlap_host_walk(int(tree.double), _p(tree.pairs), tree.root, _p(tree.bboxes), _p(tree.ids), _p(q), n, _p(order), int(original_ids),
                                  deep_cap, threads, _p(c), _p(off), lp_arg, _p(cnt)) == 0
     return c, lp, cnt
-
-
-def guards_intact(lp, total):
-    return bool((lp[:GUARD] == SENT_PRIM).all() and (lp[GUARD + total:] == SENT_PRIM).all())
 
 
 def host_overlap(dll, tree, queries, **kw):

@@ -1,4 +1,4 @@
-"""CPU: the TEXT of the radius-query kernel (bvh_amd/csrc/radius_body.inc + point_walk.inc + trace_device.h) compiled for the host by
+"""CPU: the TEXT of the radius-query kernel (bvh_amd/csrc/radius_body.inc + list_walk.inc + point_walk.inc + trace_device.h) compiled for the host by
 tests/cpp/radius_body_host.cpp. The walk over the golden trees against a brute force over the same distance functions, filtered in
 the tree's left-first depth-first order; the shapes of the output (count pass, exact offsets, fixed segments, padding, guard zones);
 edge queries; trees deeper than 64 levels; the exported symbols. The device's counts, lists and distances must equal this harness's
@@ -76,7 +76,8 @@ def host_walk(dll, tree, queries, offsets=None, total=0, counts=True, dist=True,
     return c, lp, ld, cnt
 
 
-def guards_intact(lp, ld, total):
+def guards_intact(lp, total, ld=None):
+    """The sentinels on either side of the `total` list entries (and of the distances beside them, if any) are untouched."""
     ok = (lp[:GUARD] == SENT_PRIM).all() and (lp[GUARD + total:] == SENT_PRIM).all()
     if ld is not None:
         ok = ok and (ld[:GUARD] == SENT_DIST).all() and (ld[GUARD + total:] == SENT_DIST).all()
@@ -91,7 +92,7 @@ def host_radius(dll, tree, queries, **kw):
     total = int(offsets[-1])
     c2, lp, ld, cnt = host_walk(dll, tree, queries, offsets=offsets, total=total, **kw)
     assert (c2 == counts).all() and (cnt == cnt0).all()
-    assert guards_intact(lp, ld, total)
+    assert guards_intact(lp, total, ld)
     ids, dist = lp[GUARD:GUARD + total], ld[GUARD:GUARD + total]
     if kw.get("prim_ids") is None:
         assert (ids < len(tree.prims)).all()
@@ -188,7 +189,7 @@ def test_output_shapes(dll, orc):
     assert counts.max() > 4 and (counts == 0).any() and (counts > 0).any()
     # without the optional outputs: same lists
     _, lp, ld, _ = host_walk(dll, tree, q, offsets=offsets, total=len(ids), counts=False, dist=False)
-    assert ld is None and (lp[GUARD:GUARD + len(ids)] == ids).all() and guards_intact(lp, None, len(ids))
+    assert ld is None and (lp[GUARD:GUARD + len(ids)] == ids).all() and guards_intact(lp, len(ids))
     # k = 4 slots per query, the buffer starting at a non-zero offset: prefix in walk order, padding, untruncated counts, guards
     k, base = 4, 7
     fixed = (base + k * np.arange(n + 1)).astype(np.uint64)
@@ -196,7 +197,7 @@ def test_output_shapes(dll, orc):
     c4, lp, ld, _ = host_walk(dll, tree, q, offsets=fixed, total=total)
     assert (c4 == counts).all()
     assert (lp[GUARD:GUARD + base] == SENT_PRIM).all() and (lp[GUARD + base + k * n:] == SENT_PRIM).all()
-    assert (ld[GUARD:GUARD + base] == SENT_DIST).all() and (ld[GUARD + base + k * n:] == SENT_DIST).all() and guards_intact(lp, ld, total)
+    assert (ld[GUARD:GUARD + base] == SENT_DIST).all() and (ld[GUARD + base + k * n:] == SENT_DIST).all() and guards_intact(lp, total, ld)
     seg_p = lp[GUARD + base:GUARD + base + k * n].reshape(n, k)
     seg_d = ld[GUARD + base:GUARD + base + k * n].reshape(n, k)
     for i in range(n):
@@ -210,7 +211,7 @@ def test_output_shapes(dll, orc):
     c5, lp, ld, _ = host_walk(dll, tree, q, offsets=stale, total=16)
     assert (c5 == counts).all()
     written = lp[GUARD:GUARD + 16] != SENT_PRIM
-    assert not written[9:].any() and guards_intact(lp, ld, 16)
+    assert not written[9:].any() and guards_intact(lp, 16, ld)
 
 
 def test_edge_queries(dll, orc):
