@@ -155,6 +155,8 @@ _SIGS_T = {
     "bvh{S}_knn_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_overlap_boxes": (_I, [_P, _P, _Z, _P, _Z, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_overlap_self": (_I, [_P, _P, _Z, _U, _P, _P, _P, _P, _P]),
+    "bvh{S}_instance_prepare": (_I, [_P, _Z, _P, _P, _Z, _P, _P, _P, _P]),
+    "bvh{S}_intersect_rays_instanced": (_I, [_P, _P, _Z, _P, _P, _Z, _P, _Z, _U, _P, _P, _P, _P]),
     # one ray, host leaf callback (c_api/bvh.h:277-295): (bvh, ray, callback struct)
     "bvh{S}_intersect_ray": (None, [_P, _P, _P]),
     "bvh{S}_intersect_ray_any": (None, [_P, _P, _P]),
@@ -164,7 +166,11 @@ _SIGS_T = {
 }
 
 
-class OptimizeProfile(C.Structure):         # struct bvh_amd_optimize_profile
+class Geometry(C.Structure):                  # struct bvh_amd_geometry3f / 3d: {tree handle, BVH-order PrecomputedTri in HBM}
+    _fields_ = [("bvh", C.c_void_p), ("d_tris12", C.c_void_p)]
+
+
+class OptimizeProfile(C.Structure):        # struct bvh_amd_optimize_profile
     _fields_ = [("iterations", C.c_uint), ("replayed", C.c_uint), ("replacements", C.c_ulonglong), ("heap_ms", C.c_float)]
 
 
@@ -193,6 +199,7 @@ _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_inter
             "bvh{S}_radius_search_tri", "bvh{S}_radius_search_sphere",                                # and the radius queries
             "bvh{S}_knn_tri", "bvh{S}_knn_sphere",                                                    # and the k-nearest queries
             "bvh{S}_overlap_boxes", "bvh{S}_overlap_self",                                            # and the box-overlap queries
+            "bvh{S}_instance_prepare", "bvh{S}_intersect_rays_instanced",                             # and the instanced ray queries
             "bvh{S}_refit_tris", "bvh{S}_traversal_cost")                                             # (tri.h; the 3D area term)
 
 

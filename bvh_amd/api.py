@@ -701,6 +701,88 @@ def self_overlaps(bvh: Bvh, bboxes, original_ids: bool = True, counters: bool = 
     return (pairs, out[3]) if counters else pairs
 
 
+def _geometry_table(geometries, who: str):
+    """(struct bvh_amd_geometry3X array, family suffix, torch dtype, what keeps the triangle tensors alive) of a list of (Bvh, prims12)."""
+    torch = _torch()
+    geometries = list(geometries)
+    if not geometries:
+        raise ValueError(f"{who}: at least one geometry is needed")
+    s = geometries[0][0]._s
+    dt = torch.float32 if s[1] == "f" else torch.float64
+    table = (_lib.Geometry * len(geometries))()
+    keep = []
+    for k, (bvh, prims) in enumerate(geometries):
+        if bvh._s != s or bvh.dim != 3:
+            raise TypeError(f"{who}: geometry {k} belongs to another family than geometry 0 (3D trees of one scalar type only)")
+        p = bvh._prims_in(prims, 12, who)
+        keep.append(p)
+        table[k].bvh, table[k].d_tris12 = bvh._h, p.data_ptr()
+    return table, s, dt, keep
+
+
+def _geometry_ids(geometry_ids, n: int, who: str):
+    torch = _torch()
+    if geometry_ids is None:
+        return None
+    g = _dev(geometry_ids).reshape(-1)
+    if g.dtype not in (torch.int32, torch.int64, torch.uint8, torch.int16):
+        raise TypeError(f"{who}: geometry_ids must be integers")
+    if g.shape[0] != n:
+        raise ValueError(f"{who}: one geometry id per instance")
+    return g.to(torch.int32).contiguous()
+
+
+def instance_prepare(geometries, transforms, geometry_ids=None):
+    """The instances of a two-level scene, ready for a builder or Bvh.refit_boxes (bvh3X_instance_prepare). geometries: a list of
+    (Bvh, prims12); transforms: (n, 12) or (n, 3, 4) row-major object-to-world matrices (x_world = M x_object + t); geometry_ids: (n,)
+    indices into `geometries` (None: all 0). Returns (world2obj (n, 12), bboxes (n, 6), centers (n, 3)) device tensors: the inverse
+    maps (NaN rows: a singular or non-finite transform, the instance is disabled), the conservative world boxes {min, max} of the
+    geometries' root boxes, read from the trees as they are now on the current stream, and the boxes' centres."""
+    torch = _torch()
+    table, s, dt, keep = _geometry_table(geometries, "instance_prepare")
+    m = geometries[0][0]._prims_in(transforms, 12, "instance_prepare")
+    n = m.shape[0]
+    gid = _geometry_ids(geometry_ids, n, "instance_prepare")
+    w = torch.empty((n, 12), dtype=dt, device=m.device)
+    bb = torch.empty((n, 6), dtype=dt, device=m.device)
+    cc = torch.empty((n, 3), dtype=dt, device=m.device)
+    fn = getattr(_lib.load(), f"bvh{s}_instance_prepare")
+    _lib.check(fn(table, len(table), m.data_ptr(), gid.data_ptr() if gid is not None else None, n, w.data_ptr(), bb.data_ptr(), cc.data_ptr(), _stream()),
+               "instance_prepare")
+    del keep
+    return w, bb, cc
+
+
+def intersect_instanced(top: Bvh, geometries, world2obj, rays, geometry_ids=None, any_hit: bool = False, robust: bool = False,
+                        counters: bool = False, original_ids: bool = False, out=None):
+    """Batched rays through a two-level scene (bvh3X_intersect_rays_instanced): `top` is a Bvh built over instance_prepare's boxes (its
+    prim ids are instance indices), geometries the list of (Bvh, prims12) and world2obj / geometry_ids what instance_prepare took and
+    returned. Per ray the nesting of `intersect`: the top tree is walked, an instance's geometry is walked with the ray carried into
+    its object space, every accepted hit shortens the ray for what follows. Returns (hits, instances): the (n, 4) hit records of
+    `intersect` (prim = BVH-order index in the hit geometry's tree, or its original id with original_ids) and an int32 (n,) tensor of
+    instance indices (-1 = INVALID on a miss); with counters also (pairs, tests, leaves) summed over both levels."""
+    torch = _torch()
+    table, s, dt, keep = _geometry_table(geometries, "intersect_instanced")
+    if top._s != s:
+        raise TypeError("intersect_instanced: the top tree and the geometries must belong to one 3D family")
+    w = top._prims_in(world2obj, 12, "intersect_instanced")
+    r = top._prims_in(rays, 8, "intersect_instanced")
+    n, n_inst = r.shape[0], w.shape[0]
+    gid = _geometry_ids(geometry_ids, n_inst, "intersect_instanced")
+    if out is None:
+        out = torch.empty((n, 4), dtype=dt, device=r.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() == 4 * n):
+        raise TypeError("intersect_instanced: `out` must be a contiguous (n, 4) device tensor of the trees' scalar type")
+    inst = torch.empty(n, dtype=torch.int32, device=r.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
+    flags = (RayFlags.ANY_HIT if any_hit else 0) | (RayFlags.ROBUST if robust else 0) | (8 if original_ids else 0)
+    fn = getattr(_lib.load(), f"bvh{s}_intersect_rays_instanced")
+    _lib.check(fn(top._h, table, len(table), w.data_ptr(), gid.data_ptr() if gid is not None else None, n_inst, r.data_ptr(), n, int(flags),
+                  out.data_ptr(), inst.data_ptr(), cnt.data_ptr() if counters else None, _stream()), "intersect_instanced")
+    del keep
+    return (out, inst, cnt) if counters else (out, inst)
+
+
 KNN_MAX_K = 64                                  # BVH_AMD_KNN_MAX_K
 
 

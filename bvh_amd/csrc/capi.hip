@@ -569,6 +569,24 @@ int overlap(const typename Family<T, 3>::Bvh* bvh, bool self, const T* d_bboxes,
                              static_cast<hipStream_t>(stream));
 }
 
+// bvh3X_instance_prepare / bvh3X_intersect_rays_instanced: struct bvh_amd_geometry3X is GeomRef<T> by layout (a handle is its BvhImpl).
+template <typename T, typename Geometry>
+const GeomRef<T>* geom_refs(const Geometry* geoms) {
+    static_assert(sizeof(Geometry) == sizeof(GeomRef<T>) && offsetof(Geometry, d_tris12) == offsetof(GeomRef<T>, d_tris12));
+    return reinterpret_cast<const GeomRef<T>*>(geoms);
+}
+
+template <typename T, typename Geometry>
+int intersect_instanced(const typename Family<T, 3>::Bvh* top, const Geometry* geoms, size_t n_geoms, const T* d_world2obj, const uint32_t* d_geometry,
+                        size_t n_instances, const typename Family<T, 3>::Ray* d_rays, size_t n_rays, unsigned flags, typename HitOf<T>::Type* d_hits,
+                        uint32_t* d_hit_instances, bvh_amd_counters* d_counters, void* stream)
+{
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(top, n_rays, "intersect_rays_instanced", &b)) return rc;
+    return launch_instanced<T>(*b, geom_refs<T>(geoms), n_geoms, d_world2obj, d_geometry, n_instances, reinterpret_cast<const T*>(d_rays), n_rays, flags,
+                               d_hits, d_hit_instances, d_counters, static_cast<hipStream_t>(stream));
+}
+
 // bvhXX_intersect_ray{,_any}{,_robust} (c_api/bvh.h:277-295 over bvh_impl.h:235-250): one ray, the leaves go to the caller's
 // function. The walk runs on the device (traverse.hip, ray_step_kernel); `ray` is the family's own struct.
 template <typename T, int D>
@@ -789,7 +807,15 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
         return overlap<T>(b, false, bboxes, n_boxes, queries6, n, flags, counts, offsets, list_prims, cnt, s); }        \
     int bvh##S##_overlap_self(const bvh##S* b, const T* bboxes, size_t n_boxes, unsigned flags, uint32_t* counts,        \
                               const uint64_t* offsets, uint32_t* list_prims, bvh_amd_counters* cnt, void* s) {           \
-        return overlap<T>(b, true, bboxes, n_boxes, nullptr, 0, flags, counts, offsets, list_prims, cnt, s); }
+        return overlap<T>(b, true, bboxes, n_boxes, nullptr, 0, flags, counts, offsets, list_prims, cnt, s); }                  \
+    int bvh##S##_instance_prepare(const bvh_amd_geometry##S* geoms, size_t n_geoms, const T* obj2world, const uint32_t* geometry,  \
+                                  size_t n_instances, T* world2obj, T* bboxes, T* centers, void* s) {                    \
+        return launch_instance_prepare<T>(geom_refs<T>(geoms), n_geoms, obj2world, geometry, n_instances, world2obj, bboxes, centers, \
+                                          static_cast<hipStream_t>(s)); }                                                \
+    int bvh##S##_intersect_rays_instanced(const bvh##S* top, const bvh_amd_geometry##S* geoms, size_t n_geoms, const T* world2obj, \
+                                          const uint32_t* geometry, size_t n_instances, const bvh_ray##S* rays, size_t n_rays,     \
+                                          unsigned flags, bvh_hit##S* hits, uint32_t* hit_instances, bvh_amd_counters* cnt, void* s) { \
+        return intersect_instanced<T>(top, geoms, n_geoms, world2obj, geometry, n_instances, rays, n_rays, flags, hits, hit_instances, cnt, s); }
 
 #define BVH_AMD_IMPL_RAY(T, D, S, CB, VIS)                                                                          \
     void bvh##S##_intersect_ray(const bvh##S* b, const bvh_ray##S* r, const CB* cb) { intersect_ray_legacy<T, D>(impl<T, D>(b), r, cb, 0u); } \

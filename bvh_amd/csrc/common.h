@@ -278,6 +278,18 @@ int offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets,
 template <typename T>
 int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_boxes, const T* d_queries6, size_t n, unsigned flags, uint32_t* d_counts,
                    const uint64_t* d_offsets, uint32_t* d_list_prims, bvh_amd_counters* d_counters, hipStream_t stream);
+// instanced.hip: two-level scenes. A geometry = {tree, its BVH-order PrecomputedTri} (the layout of struct bvh_amd_geometry3f / 3d).
+// launch_instance_prepare: n_instances x object-to-world 3 x 4 -> world-to-object 3 x 4 (NaN: disabled), world boxes {min, max},
+// centres. launch_instanced: n_rays through `top` (built over those boxes, prim ids = instance indices) and the instances' geometries ->
+// one hit record and one instance index per ray (flags: ANY_HIT, ROBUST, ORIGINAL_IDS, UNSORTED)
+template <typename T> struct GeomRef { const BvhImpl<T>* bvh; const T* d_tris12; };
+template <typename T>
+int launch_instance_prepare(const GeomRef<T>* geoms, size_t n_geoms, const T* d_obj2world, const uint32_t* d_geometry, size_t n_instances,
+                            T* d_world2obj, T* d_bboxes, T* d_centers, hipStream_t stream);
+template <typename T>
+int launch_instanced(const BvhImpl<T>& top, const GeomRef<T>* geoms, size_t n_geoms, const T* d_world2obj, const uint32_t* d_geometry,
+                     size_t n_instances, const T* d_rays, size_t n_rays, unsigned flags, typename HitOf<T>::Type* d_hits, uint32_t* d_hit_instances,
+                     bvh_amd_counters* d_counters, hipStream_t stream);
 // knn.hip: batched k-nearest queries, n x {x, y, z, max_distance} -> per query a row of k {index, distance} slots in ascending
 // (distance^2, index) order, padded with {INVALID, max_distance} (flags: ORIGINAL_IDS, SORTED, UNSORTED)
 template <typename T>

@@ -147,8 +147,8 @@ template <int Lds>
 __device__ inline uint32_t stack_small_at(uint32_t sp) {
     return sp - Lds < uint32_t(kPointSmall - Lds - 1) ? sp - Lds : uint32_t(kPointSmall - Lds - 1);
 }
-template <typename T>
-__device__ inline unsigned long long stack_deep_at(const PointArgs<T>& a, unsigned long long lane, uint32_t sp) {
+template <typename Args>                                      // (PointArgs<T>, or any argument block with a deep_cap: instanced_body.inc)
+__device__ inline unsigned long long stack_deep_at(const Args& a, unsigned long long lane, uint32_t sp) {
     const uint32_t i = sp - kPointSmall;
     return lane * a.deep_cap + (i < a.deep_cap ? i : a.deep_cap - 1);
 }

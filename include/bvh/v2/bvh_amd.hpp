@@ -324,6 +324,9 @@ template <> struct Api<float, 3> {
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_boxes(h, static_cast<const float*>(bb), nb, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_self(h, static_cast<const float*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
+    using CGeometry = bvh_amd_geometry3f;
+    static int instance_prepare(const CGeometry* g, size_t ng, const void* m, const uint32_t* gid, size_t n, void* w, void* bb, void* cc) { return bvh3f_instance_prepare(g, ng, static_cast<const float*>(m), gid, n, static_cast<float*>(w), static_cast<float*>(bb), static_cast<float*>(cc), nullptr); }
+    static int trace_instanced(const Handle* top, const CGeometry* g, size_t ng, const void* w, const uint32_t* gid, size_t n, const void* rays, size_t nr, unsigned f, void* hits, uint32_t* inst) { return bvh3f_intersect_rays_instanced(top, g, ng, static_cast<const float*>(w), gid, n, static_cast<const bvh_ray3f*>(rays), nr, f, static_cast<bvh_hit3f*>(hits), inst, nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, float*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitorf v{ user, leaf, inner };
         return bvh3f_intersect_ray_visit(h, static_cast<const bvh_ray3f*>(ray), start, f, &v);
@@ -364,6 +367,9 @@ template <> struct Api<double, 3> {
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_boxes(h, static_cast<const double*>(bb), nb, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_self(h, static_cast<const double*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
+    using CGeometry = bvh_amd_geometry3d;
+    static int instance_prepare(const CGeometry* g, size_t ng, const void* m, const uint32_t* gid, size_t n, void* w, void* bb, void* cc) { return bvh3d_instance_prepare(g, ng, static_cast<const double*>(m), gid, n, static_cast<double*>(w), static_cast<double*>(bb), static_cast<double*>(cc), nullptr); }
+    static int trace_instanced(const Handle* top, const CGeometry* g, size_t ng, const void* w, const uint32_t* gid, size_t n, const void* rays, size_t nr, unsigned f, void* hits, uint32_t* inst) { return bvh3d_intersect_rays_instanced(top, g, ng, static_cast<const double*>(w), gid, n, static_cast<const bvh_ray3d*>(rays), nr, f, static_cast<bvh_hit3d*>(hits), inst, nullptr, nullptr); }
     static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, double*, size_t, size_t), void (*inner)(void*, size_t)) {
         const bvh_amd_ray_visitord v{ user, leaf, inner };
         return bvh3d_intersect_ray_visit(h, static_cast<const bvh_ray3d*>(ray), start, f, &v);
@@ -425,6 +431,9 @@ template <typename T> struct Hit;
 template <> struct Hit<float>  { uint32_t prim; float t, u, v; static constexpr uint32_t invalid = BVH_AMD_INVALID; };
 template <> struct Hit<double> { uint32_t prim; uint32_t pad; double t, u, v; static constexpr uint32_t invalid = BVH_AMD_INVALID; };
 static_assert(sizeof(Hit<float>) == sizeof(bvh_hit3f) && sizeof(Hit<double>) == sizeof(bvh_hit3d));
+
+// An affine map of a two-level scene, row-major 3 x 4: x' = M x + t with t in column 3 (bvh3X_instance_prepare).
+template <typename T> struct Affine { T m[12]; };
 
 // One closest-point query (bvhXX_closest_points_*): the point and the largest distance of interest (+inf: unbounded).
 template <typename T> struct PointQuery { Vec<T, 3> p; T max_distance; };
@@ -1044,6 +1053,55 @@ void overlap_self_batch(const Bvh<Node>& bvh, const DeviceArray<BBox<typename No
     static_assert(Node::dimension == 3, "overlap queries: 3D trees only");
     detail::overlap_host([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
         return Api<T, 3>::overlap_self(bvh.device(), bboxes.data(), bboxes.size(), flags, c, o, l); }, bvh.prim_ids.size(), offsets, list_prims, "overlap_self");
+}
+
+// Two-level scenes (include/bvh_amd.h: bvh3X_instance_prepare / bvh3X_intersect_rays_instanced): a table of geometries {tree, its
+// BVH-order triangles}, instances {object-to-world map, geometry index} and a top tree built over the instances' world boxes, whose
+// prim ids are instance indices. A Geometry points at a Bvh and a triangle array that outlive the calls.
+template <typename Node>
+struct Geometry {
+    const Bvh<Node>* bvh;
+    const DeviceArray<PrecomputedTri<typename Node::Scalar>>* prims;
+};
+namespace detail {
+template <typename Node>
+std::vector<typename Api<typename Node::Scalar, 3>::CGeometry> geometry_table(std::span<const Geometry<Node>> geoms) {
+    static_assert(Node::dimension == 3, "instanced ray queries: 3D trees only");
+    std::vector<typename Api<typename Node::Scalar, 3>::CGeometry> table;
+    for (const Geometry<Node>& g : geoms) table.push_back({ g.bvh->device(), reinterpret_cast<const typename Node::Scalar*>(g.prims->data()) });
+    return table;
+}
+} // namespace detail
+// Per instance: the inverse map (twelve NaNs: singular or non-finite, the instance is disabled), the conservative world box of its
+// geometry's root box and that box's centre, what the builders and refit_boxes take. `geometry`: one index per instance, or null: all 0.
+// The outputs are resized to obj2world.size() if they have another size.
+template <typename Node>
+void instance_prepare(std::span<const Geometry<Node>> geoms, const DeviceArray<Affine<typename Node::Scalar>>& obj2world, const DeviceArray<uint32_t>* geometry,
+                      DeviceArray<Affine<typename Node::Scalar>>& world2obj, DeviceArray<BBox<typename Node::Scalar, 3>>& bboxes,
+                      DeviceArray<Vec<typename Node::Scalar, 3>>& centers) {
+    using T = typename Node::Scalar;
+    const size_t n = obj2world.size();
+    if (geometry && geometry->size() < n) throw Error("instance_prepare: one geometry index per instance");
+    if (world2obj.size() != n) world2obj = DeviceArray<Affine<T>>(n);
+    if (bboxes.size() != n) bboxes = DeviceArray<BBox<T, 3>>(n);
+    if (centers.size() != n) centers = DeviceArray<Vec<T, 3>>(n);
+    const auto table = detail::geometry_table(geoms);
+    check(Api<T, 3>::instance_prepare(table.data(), table.size(), obj2world.data(), geometry ? geometry->data() : nullptr, n, world2obj.data(), bboxes.data(),
+                                      centers.data()), "instance_prepare");
+}
+// Bvh::intersect<IsAnyHit, IsRobust> nested through the instances: per ray the hit record of intersect_batch (prim = BVH-order index
+// in the hit geometry's tree, or its original id with BVH_AMD_RAY_ORIGINAL_IDS in `flags`) and the instance (BVH_AMD_INVALID on a miss).
+template <bool IsAnyHit, bool IsRobust, typename Node>
+void intersect_instanced_batch(const Bvh<Node>& top, std::span<const Geometry<Node>> geoms, const DeviceArray<Affine<typename Node::Scalar>>& world2obj,
+                               const DeviceArray<uint32_t>* geometry, const DeviceArray<Ray<typename Node::Scalar, 3>>& rays,
+                               DeviceArray<Hit<typename Node::Scalar>>& hits, DeviceArray<uint32_t>& instances, unsigned flags = 0) {
+    using T = typename Node::Scalar;
+    if (hits.size() < rays.size() || instances.size() < rays.size()) throw Error("intersect_instanced_batch: one hit record and one instance per ray");
+    if (geometry && geometry->size() < world2obj.size()) throw Error("intersect_instanced_batch: one geometry index per instance");
+    flags |= (IsAnyHit ? unsigned(BVH_AMD_RAY_ANY_HIT) : 0u) | (IsRobust ? unsigned(BVH_AMD_RAY_ROBUST) : 0u);
+    const auto table = detail::geometry_table(geoms);
+    check(Api<T, 3>::trace_instanced(top.device(), table.data(), table.size(), world2obj.data(), geometry ? geometry->data() : nullptr, world2obj.size(),
+                                     rays.data(), rays.size(), flags, hits.data(), instances.data()), "intersect_rays_instanced");
 }
 
 // For each query, the k nearest primitives within its max_distance (include/bvh_amd.h: bvhXX_knn_*), k in [1, BVH_AMD_KNN_MAX_K]: row q

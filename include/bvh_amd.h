@@ -618,6 +618,47 @@ BVH_AMD_API int bvh3f_overlap_self(const struct bvh3f*, const float* d_bboxes, s
 BVH_AMD_API int bvh3d_overlap_self(const struct bvh3d*, const double* d_bboxes, size_t n_boxes, unsigned flags,
     uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
 
+/* ---- batched instanced ray queries: a two-level scene with transforms ---------------------------------------------------------- */
+/* A scene is a table of geometries {tree, its BVH-order PrecomputedTri, as bvh3X_intersect_rays_tri takes them}, n_instances
+ * instances {object-to-world matrix, geometry index}, and a top tree: an ordinary bvh3X built over the instances' world boxes,
+ * whose prim ids are instance indices. Matrices are row-major 3 x 4 (12 scalars): x_world = M x_object + t, t in column 3.
+ * d_geometry holds one uint32 per instance, or is NULL: every instance uses geometry 0.
+ *
+ * bvh3X_instance_prepare, one launch: per instance the world-to-object matrix (adjugate / determinant; a zero determinant or
+ * anything non-finite DISABLES the instance: twelve NaNs), the world box of its geometry's root box {min.xyz, max.xyz}, widened so
+ * that it is conservative under rounding (by at most 12 eps (sum_j |m_ij| max(|lo_j|, |hi_j|) + |t_i|) per axis), and that box's
+ * centre — the arrays bvhXX_build_device and bvhXX_refit_boxes take. A disabled instance, or one whose geometry index is outside the
+ * table, gets the zero-extent box at its translation (at the origin when that is not finite). The root boxes are read from the
+ * geometries' resident nodes on the stream: a geometry refitted on it before the call is seen. Rigid motion therefore needs no
+ * geometry rebuild: new matrices -> bvh3X_instance_prepare -> bvh3X_refit_boxes on the top tree -> trace.
+ *
+ * bvh3X_intersect_rays_instanced: per ray exactly the nesting of the single-level query. The top tree is walked as
+ * Bvh::intersect<IsAnyHit, IsRobust> walks; at a top leaf its slots are taken in order; an instance that is enabled and whose
+ * geometry index is inside the table gets the ray in its object space (org' = W org + w, dir' = W dir, tmin and the current tmax
+ * unchanged; the direction is not normalised, so t means the same in both spaces; a -0 component may come out +0) and its tree is
+ * walked from its root with the same rules and the triangle test of bvh3X_intersect_rays_tri. An accepted hit shortens tmax for
+ * everything after it, in both levels; any-hit ends at the first geometry leaf that leaves a hit. d_hits[r] = {prim = BVH-order
+ * index in the hit geometry's tree (its prim_ids[...] with BVH_AMD_RAY_ORIGINAL_IDS), t, u, v}, d_hit_instances[r] = the instance; a
+ * miss is {BVH_AMD_INVALID, the ray's tmax, 0, 0} and instance BVH_AMD_INVALID. A ray whose tmin or tmax is NaN is a miss and counts
+ * nothing. d_counters (optional) sums both levels: pair records fetched, triangles tested, leaves visited (a top leaf once).
+ * flags: BVH_AMD_RAY_ANY_HIT, BVH_AMD_RAY_ROBUST, BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_UNSORTED (what happens anyway: the batch is
+ * never reordered); BVH_AMD_RAY_SORTED and any other bit: BVH_AMD_ERR_ARG. n_rays == 0 is a no-op. n_instances must exceed the
+ * top tree's largest prim id (checked once per layout). Re-entrant on const trees (no work slot is claimed); the call synchronises
+ * nothing (the first call on a layout measures the trees' depths). Not offered: spheres, the 2D families, more than two levels,
+ * mixed scalar types, reordering of the batch. */
+struct bvh_amd_geometry3f { const struct bvh3f* bvh; const float* d_tris12; };
+struct bvh_amd_geometry3d { const struct bvh3d* bvh; const double* d_tris12; };
+BVH_AMD_API int bvh3f_instance_prepare(const struct bvh_amd_geometry3f* geoms, size_t n_geoms, const float* d_obj2world12, const uint32_t* d_geometry,
+    size_t n_instances, float* d_world2obj12, float* d_bboxes, float* d_centers, void* stream);
+BVH_AMD_API int bvh3d_instance_prepare(const struct bvh_amd_geometry3d* geoms, size_t n_geoms, const double* d_obj2world12, const uint32_t* d_geometry,
+    size_t n_instances, double* d_world2obj12, double* d_bboxes, double* d_centers, void* stream);
+BVH_AMD_API int bvh3f_intersect_rays_instanced(const struct bvh3f* top, const struct bvh_amd_geometry3f* geoms, size_t n_geoms,
+    const float* d_world2obj12, const uint32_t* d_geometry, size_t n_instances, const struct bvh_ray3f* d_rays, size_t n_rays, unsigned flags,
+    struct bvh_hit3f* d_hits, uint32_t* d_hit_instances, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_intersect_rays_instanced(const struct bvh3d* top, const struct bvh_amd_geometry3d* geoms, size_t n_geoms,
+    const double* d_world2obj12, const uint32_t* d_geometry, size_t n_instances, const struct bvh_ray3d* d_rays, size_t n_rays, unsigned flags,
+    struct bvh_hit3d* d_hits, uint32_t* d_hit_instances, struct bvh_amd_counters* d_counters, void* stream);
+
 /* Optional, additive: pays NOW what the first large batch through a fresh tree would pay inside its own call — the tree's depth /
  * expected-visits pass (one read-back) and the first allocation of the ray-reordering scratch for batches of `n_rays_hint` rays (kept
  * in the library's block cache for that stream). A single Bvh::intersect on a fresh Bvh is the reference's normal use (bvh.h:160-182);
