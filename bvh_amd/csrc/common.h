@@ -302,6 +302,8 @@ int set_experiment(const char* name, int value);                             // 
 void set_tuning(int refill, int leaf, int coop, int parts);               // traverse.hip: per-thread overrides for A/B runs (< 0: default)
 const char* last_kernel_name();
 bool last_launch_reordered();
+int last_query_launches();                                    // traverse.hip: set by point_query_run (point_query.h) and launch_instanced
+void set_last_query_launches(int launches);
 void kernel_timing(bool on);                                  // traverse.hip
 int kernel_times(float* ms_out, size_t capacity, size_t* count_out);
 int reorder_times(float* ms_out, size_t capacity, size_t* count_out);

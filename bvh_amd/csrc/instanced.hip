@@ -173,6 +173,7 @@ int launch_instanced(const BvhImpl<T>& top, const GeomRef<T>* geoms, size_t n_ge
         return fail(BVH_AMD_ERR_ARG, who + ": " + std::to_string(n_instances) + " instances given, but the top tree's prim_ids refer to instance " +
                     std::to_string(largest));
 
+    set_last_query_launches(0);                               // (bvh_amd_last_query_launches: the checks are passed; counted below, one per launch)
     // the stack's bound: depth(top) + the marker + the deepest geometry (cached per layout)
     if (const int rc = tree_depth<T>(top, stream)) return rc;
     int bound = top.max_depth.load() + 1, deepest = 0;
@@ -200,6 +201,7 @@ int launch_instanced(const BvhImpl<T>& top, const GeomRef<T>* geoms, size_t n_ge
         if (e != hipSuccess) { deep.mem = nullptr; return fail(BVH_AMD_ERR_HIP, who + ": stack spill buffer: " + hipGetErrorString(e)); }
         deep_cap = static_cast<uint32_t>(cap);
     }
+    int launches = 0;
     for (size_t first = 0; first < n_rays; first += per_launch) {
         auto fill = [&](auto& x) {
             x.top_pairs = top.d_pairs; x.top_prim_ids = top.d_prim_ids; x.world2obj = d_world2obj; x.geometry = d_geometry; x.rays = d_rays;
@@ -215,6 +217,7 @@ int launch_instanced(const BvhImpl<T>& top, const GeomRef<T>* geoms, size_t n_ge
                             : point_query_launch(instanced_kernel<T, any(), robust(), stats(), dp(), false>, b, kBlock, 0, stream);
         });
         if (rc) return rc;
+        set_last_query_launches(++launches);
     }
     return BVH_AMD_OK;
 }

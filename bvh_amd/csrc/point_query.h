@@ -51,6 +51,7 @@ template <typename T, bool Boxes = false, typename Launch>
 int point_query_run(const BvhImpl<T>& b, const T* d_prims, const T* d_queries, size_t n, unsigned flags, bvh_amd_counters* d_counters, size_t entry,
                     size_t lanes, size_t sort_min, int key_bits, const char* who, hipStream_t stream, Launch launch) {
     StreamScope scope(stream);
+    set_last_query_launches(0);                               // (bvh_amd_last_query_launches: counted below, one per launch)
     void* deep_mem = nullptr;
     void* sort_mem = nullptr;
     ScratchTag deep_tag, sort_tag;
@@ -88,11 +89,13 @@ int point_query_run(const BvhImpl<T>& b, const T* d_prims, const T* d_queries, s
         if (rc) return release(rc);
     }
 
+    int launches = 0;
     for (size_t first = 0; first < n; first += per_launch) {
         a.first = first;
         a.n = std::min(per_launch, n - first);
         const int rc = launch(a, static_cast<T*>(deep_mem));
         if (rc) return release(rc);
+        set_last_query_launches(++launches);
     }
     return release(BVH_AMD_OK);
 }

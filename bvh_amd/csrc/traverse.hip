@@ -36,6 +36,7 @@ namespace {
 
 thread_local const char* g_last_kernel = "";
 thread_local bool g_last_reordered = false;
+thread_local int g_last_query_launches = 0;                   // walk-kernel launches of the calling thread's latest point / box / instanced query
 thread_local int g_last_plan[4] = {0, 0, 0, 0};               // reordered, coop, refill, leaf of the calling thread's latest launch
 
 // Optional timing of the traversal kernel alone (bench.py's roofline: the coherence sort in front of it is not the kernel):
@@ -583,6 +584,8 @@ void last_plan_search(float ns_per_ray[5], int measurements[5], unsigned* droppe
 }
 const char* last_kernel_name() { return g_last_kernel; }
 bool last_launch_reordered() { return g_last_reordered; }
+int last_query_launches() { return g_last_query_launches; }
+void set_last_query_launches(int launches) { g_last_query_launches = launches; }
 
 void kernel_timing(bool on) {
     KernelTimer& t = kernel_timer();

@@ -692,6 +692,11 @@ BVH_AMD_API int bvh_amd_radix_sort_pairs_u32(uint32_t* d_keys, uint32_t* d_vals,
 BVH_AMD_API const char* bvh_amd_last_kernel_name(void);
 /* 1 when the calling thread's latest 3D batch traversal reordered its rays internally (BVH_AMD_RAY_SORTED, or the default rule). */
 BVH_AMD_API int bvh_amd_last_launch_reordered(void);
+/* The number of walk-kernel launches the calling thread's latest point, box or instanced ray query made: 1, or one per slice of a
+ * batch over a tree deeper than 64 levels that was cut to bound the stack spill. 0 before the first such query. A call that is
+ * refused by its argument checks or has an empty batch leaves the value as it was; a call that fails after them (an allocation, a
+ * launch) leaves the number of launches it made before it failed, 0 if none. */
+BVH_AMD_API int bvh_amd_last_query_launches(void);
 /* Measurement aid: with timing on, every batch traversal launched by the calling thread records a pair of events on its stream
  * around the traversal kernel alone (not the optional ray reordering in front of it). bvh_amd_kernel_times waits for and returns
  * the durations (ms) of the latest min(capacity, 256) launches since timing was switched on, oldest first. */

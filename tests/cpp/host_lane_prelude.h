@@ -1,7 +1,8 @@
-// TEST INFRASTRUCTURE (CPU, no GPU): what the host harnesses of the point queries (closest_body_host.cpp, radius_body_host.cpp,
-// knn_body_host.cpp, overlap_body_host.cpp) put in front of the kernels' text: single-lane stand-ins for hip_runtime.h and for
-// bvh_amd/csrc/common.h, then the device helpers of bvh_amd/csrc/trace_device.h, and the thread-split scaffold of their walks. The
-// stand-ins must follow common.h (PairNode, kCountBits, LEAF_*).
+// TEST INFRASTRUCTURE (CPU, no GPU): what the host harnesses of the point, box and instanced queries (closest_body_host.cpp,
+// radius_body_host.cpp, knn_body_host.cpp, overlap_body_host.cpp, instanced_body_host.cpp) put in front of the kernels' text:
+// single-lane stand-ins for hip_runtime.h and for bvh_amd/csrc/common.h, then the device helpers of bvh_amd/csrc/trace_device.h, the
+// thread-split scaffold of their walks, and the emulation of one launch of a sliced batch over a deep tree. The stand-ins must follow
+// common.h (PairNode, kCountBits, LEAF_*).
 #pragma once
 
 #include <algorithm>
@@ -69,3 +70,52 @@ void run_lanes(size_t n, int threads, unsigned long long* counters3, Range range
     for (auto& th : pool) th.join();
     for (int k = 0; k < 3; ++k) { counters3[k] = 0; for (int t = 0; t < nt; ++t) counters3[k] += sums[3 * size_t(t) + k]; }
 }
+
+// ---- one emulated launch of a sliced batch (point_query.h, point_query_run: a tree deeper than 64 levels, slots [first, first + n) of
+// the batch, the HBM spill sized for the launch's lanes and shared by them) ----------------------------------------------------------
+// An HBM spill array of `entries` elements between two guard zones, every byte kSpillByte before the walk. The zone behind it is long
+// enough for a lane that indexed the spill by its SLOT, or a spill sized for one lane only, to land in the zone and not in foreign
+// memory: (first + launch_lanes) * deep_cap entries and kSpillGuard more.
+constexpr size_t kSpillGuard = 64;
+constexpr unsigned char kSpillByte = 0xC3;                     // (0xC3C3C3C3: as a node word a leaf at primitive 2 * 10^8, as a distance negative: neither is ever pushed)
+
+template <typename V>
+class GuardedSpill {
+public:
+    GuardedSpill(size_t first, size_t launch_lanes, size_t deep_cap)
+        : entries_(launch_lanes * deep_cap), bytes_((kSpillGuard + launch_lanes * deep_cap + (first + launch_lanes) * deep_cap + kSpillGuard) * sizeof(V), kSpillByte) {}
+    V* data() { return reinterpret_cast<V*>(bytes_.data()) + kSpillGuard; }
+    bool guards_intact() const {
+        const size_t lo = kSpillGuard * sizeof(V), hi = (kSpillGuard + entries_) * sizeof(V);
+        for (size_t i = 0; i < lo; ++i) if (bytes_[i] != kSpillByte) return false;
+        for (size_t i = hi; i < bytes_.size(); ++i) if (bytes_[i] != kSpillByte) return false;
+        return true;
+    }
+    // entries of the spill the launch wrote to
+    long long overwritten() const {
+        long long count = 0;
+        for (size_t e = 0; e < entries_; ++e) {
+            const unsigned char* p = bytes_.data() + (kSpillGuard + e) * sizeof(V);
+            bool touched = false;
+            for (size_t i = 0; i < sizeof(V); ++i) touched |= p[i] != kSpillByte;
+            count += touched;
+        }
+        return count;
+    }
+private:
+    size_t entries_;
+    std::vector<unsigned char> bytes_;
+};
+
+// The lanes 0 .. n-1 of the launch, one after the other as the device numbers them: lane_fn(lane, tid = lane % block, cnt) walks slot
+// first + lane with the spill index `lane` and the LDS column `tid` of one LDS stand-in shared by the launch; counters3 = their sum.
+template <typename Lane>
+void run_slice(size_t n, unsigned block, unsigned long long* counters3, Lane lane_fn) {
+    unsigned long long cnt[3] = {0, 0, 0};
+    for (unsigned long long lane = 0; lane < n; ++lane) lane_fn(lane, int(lane % block), cnt);
+    for (int k = 0; k < 3; ++k) counters3[k] = cnt[k];
+}
+
+// What a slice entry returns: the spill entries the launch overwrote (>= 0), or one of these.
+constexpr long long kSliceGuardBroken = -1;                   // a guard zone of the spill (or of the LDS stand-in) was written to
+constexpr long long kSliceBadArgs = -2;                       // deep_cap == 0, n > launch_lanes, ...

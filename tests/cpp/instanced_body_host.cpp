@@ -59,6 +59,31 @@ int walk(const void* top_pairs, uint32_t top_root, const uint32_t* top_prim_ids,
     return 0;
 }
 
+// One launch of a sliced batch as the device runs it (prelude: GuardedSpill, run_slice): the spill sized for the launch's lanes.
+template <typename T>
+long long walk_slice(const void* top_pairs, uint32_t top_root, const uint32_t* top_prim_ids, uint32_t n_geoms, const void* const* g_pairs,
+                     const void* const* g_tris, const uint32_t* const* g_prim_ids, const uint32_t* g_root, const void* world2obj, const uint32_t* geometry,
+                     const void* rays, size_t first, size_t n, size_t launch_lanes, int any, int robust, int original_ids, uint32_t deep_cap, void* hits,
+                     uint32_t* hit_instances, unsigned long long* counters3) {
+    if (deep_cap == 0 || n > launch_lanes) return kSliceBadArgs;
+    const std::vector<InstGeom<T>> table = geom_table<T>(n_geoms, g_pairs, g_tris, g_prim_ids, nullptr, g_root);
+    InstancedArgs<T, false> a{};
+    a.top_pairs = static_cast<const PairNode<T>*>(top_pairs); a.top_prim_ids = top_prim_ids; a.world2obj = static_cast<const T*>(world2obj);
+    a.geometry = geometry; a.rays = static_cast<const T*>(rays); a.hits = static_cast<typename HitOf<T>::Type*>(hits); a.hit_instances = hit_instances;
+    a.n = n; a.first = first; a.deep_cap = deep_cap; a.top_root = top_root; a.n_geoms = n_geoms; a.original_ids = original_ids ? 1u : 0u;
+    a.geoms.g = table.data();
+    GuardedSpill<uint32_t> deep_nodes(first, launch_lanes, deep_cap);
+    a.deep_nodes = deep_nodes.data();
+    std::vector<uint32_t> lds_node(size_t(kInstLds) * kBlock);
+    run_slice(n, kBlock, counters3, [&](unsigned long long lane, int tid, unsigned long long (&cnt)[3]) {
+        auto go = [&](auto an, auto ro) { instanced_lane<T, an(), ro(), true, true, false>(a, first + lane, lds_node.data(), tid, lane, cnt); };
+        if (any) { if (robust) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
+        else { if (robust) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
+    });
+    if (!deep_nodes.guards_intact()) return kSliceGuardBroken;
+    return deep_nodes.overwritten();
+}
+
 template <typename T>
 int prepare(uint32_t n_geoms, const void* const* g_root_box, const void* obj2world, const uint32_t* geometry, size_t n, void* world2obj, void* bboxes,
             void* centers) {
@@ -88,6 +113,21 @@ int instanced_host_walk(int is_double, const void* top_pairs, uint32_t top_root,
                             original_ids, deep_cap, threads, hits, hit_instances, counters3);
     return walk<float>(top_pairs, top_root, top_prim_ids, n_geoms, g_pairs, g_tris, g_prim_ids, g_root, world2obj, geometry, rays, n, any, robust,
                        original_ids, deep_cap, threads, hits, hit_instances, counters3);
+}
+
+// One launch of a batch that the instanced driver cut into slices (deep_cap > 0): rays [first, first + n) as the device walks them —
+// a.first = first, ray = first + lane, lane = 0 .. n-1 indexing a spill of launch_lanes * deep_cap entries that the launch's lanes
+// share, tid = lane % 256 in one LDS stand-in. rays, hits and hit_instances are the whole batch's. Returns the spill entries the
+// launch overwrote, -1 if a guard zone around the spill was written to, -2 for deep_cap == 0 or n > launch_lanes.
+long long instanced_host_walk_slice(int is_double, const void* top_pairs, uint32_t top_root, const uint32_t* top_prim_ids, uint32_t n_geoms,
+                                    const void* const* g_pairs, const void* const* g_tris, const uint32_t* const* g_prim_ids, const uint32_t* g_root,
+                                    const void* world2obj, const uint32_t* geometry, const void* rays, size_t first, size_t n, size_t launch_lanes, int any,
+                                    int robust, int original_ids, uint32_t deep_cap, void* hits, uint32_t* hit_instances, unsigned long long* counters3) {
+    if (is_double)
+        return walk_slice<double>(top_pairs, top_root, top_prim_ids, n_geoms, g_pairs, g_tris, g_prim_ids, g_root, world2obj, geometry, rays, first, n,
+                                  launch_lanes, any, robust, original_ids, deep_cap, hits, hit_instances, counters3);
+    return walk_slice<float>(top_pairs, top_root, top_prim_ids, n_geoms, g_pairs, g_tris, g_prim_ids, g_root, world2obj, geometry, rays, first, n,
+                             launch_lanes, any, robust, original_ids, deep_cap, hits, hit_instances, counters3);
 }
 
 // The kernel's instance preparation: g_root_box[k] = {minx, maxx, miny, maxy, minz, maxz} of geometry k's root; obj2world 12 per

@@ -63,6 +63,33 @@ int walk(const void* pairs, uint32_t root_index, const void* prims, const void* 
     return lds_overrun ? 2 : 0;
 }
 
+// One launch of a sliced batch as the device runs it (prelude: GuardedSpill, run_slice): both spill arrays sized for the launch's
+// lanes, one block's LDS (`stride` lanes wide, between its sentinels) shared by the launch.
+template <typename T, int Leaf>
+long long walk_slice(const void* pairs, uint32_t root_index, const void* prims, const void* queries, size_t first, size_t n, size_t launch_lanes, uint32_t k,
+                     uint32_t stride, const uint32_t* order, const uint32_t* prim_ids, uint32_t deep_cap, uint32_t* out_prims, void* out_dist, uint32_t* counts,
+                     unsigned long long* counters3) {
+    if (k == 0 || k > BVH_AMD_KNN_MAX_K || stride == 0 || stride % 2 != 0 || deep_cap == 0 || n > launch_lanes) return kSliceBadArgs;
+    KnnArgs<T> a{};
+    a.pairs = static_cast<const PairNode<T>*>(pairs); a.prims = static_cast<const T*>(prims); a.queries = static_cast<const T*>(queries);
+    a.out_prims = out_prims; a.out_dist = static_cast<T*>(out_dist); a.counts = counts; a.k = k;
+    a.n = n; a.first = first; a.order = order; a.prim_ids = prim_ids; a.counters = nullptr;
+    a.deep_cap = deep_cap; a.root_index = root_index;
+    GuardedSpill<uint32_t> deep_nodes(first, launch_lanes, deep_cap);
+    GuardedSpill<T> deep_d2(first, launch_lanes, deep_cap);
+    a.deep_nodes = deep_nodes.data(); a.deep_d2 = deep_d2.data();
+    const size_t words = knn_lds_bytes<T>(k, stride) / 8;
+    std::vector<unsigned long long> raw(words + 2 * kLdsGuardWords, kLdsSentinel);
+    const KnnLds<T> lds = knn_lds_carve<T>(raw.data() + kLdsGuardWords, k, stride);
+    run_slice(n, stride, counters3, [&](unsigned long long lane, int tid, unsigned long long (&cnt)[3]) {
+        knn_lane<T, Leaf, true, true>(a, first + lane, lds, stride, tid, lane, cnt);
+    });
+    for (size_t w = 0; w < kLdsGuardWords; ++w)
+        if (raw[w] != kLdsSentinel || raw[kLdsGuardWords + words + w] != kLdsSentinel) return kSliceGuardBroken;
+    if (!deep_nodes.guards_intact() || !deep_d2.guards_intact()) return kSliceGuardBroken;
+    return deep_nodes.overwritten() + deep_d2.overwritten();
+}
+
 } // namespace
 
 extern "C" {
@@ -81,6 +108,22 @@ int knn_host_walk(int is_double, int leaf, const void* pairs, uint32_t root_inde
     }
     if (leaf == LEAF_SPHERE) return walk<float, LEAF_SPHERE>(pairs, root_index, prims, queries, n, k, stride, order, prim_ids, deep_cap, threads, out_prims, out_dist, counts, counters3);
     return walk<float, LEAF_TRIANGLE>(pairs, root_index, prims, queries, n, k, stride, order, prim_ids, deep_cap, threads, out_prims, out_dist, counts, counters3);
+}
+
+// One launch of a batch that point_query_run cut into slices (deep_cap > 0): slots [first, first + n) as the device walks them —
+// a.first = first, slot = first + lane, lane = 0 .. n-1 indexing spill arrays of launch_lanes * deep_cap entries that the launch's
+// lanes share, tid = lane % stride in one block's LDS. queries, order and the outputs are the whole batch's. Returns the spill
+// entries the launch overwrote (both arrays), -1 if a guard zone around a spill array or the LDS was written to, -2 for arguments
+// out of range (k, stride, deep_cap == 0, n > launch_lanes).
+long long knn_host_walk_slice(int is_double, int leaf, const void* pairs, uint32_t root_index, const void* prims, const void* queries, size_t first, size_t n,
+                              size_t launch_lanes, uint32_t k, uint32_t stride, const uint32_t* order, const uint32_t* prim_ids, uint32_t deep_cap,
+                              uint32_t* out_prims, void* out_dist, uint32_t* counts, unsigned long long* counters3) {
+    if (is_double) {
+        if (leaf == LEAF_SPHERE) return walk_slice<double, LEAF_SPHERE>(pairs, root_index, prims, queries, first, n, launch_lanes, k, stride, order, prim_ids, deep_cap, out_prims, out_dist, counts, counters3);
+        return walk_slice<double, LEAF_TRIANGLE>(pairs, root_index, prims, queries, first, n, launch_lanes, k, stride, order, prim_ids, deep_cap, out_prims, out_dist, counts, counters3);
+    }
+    if (leaf == LEAF_SPHERE) return walk_slice<float, LEAF_SPHERE>(pairs, root_index, prims, queries, first, n, launch_lanes, k, stride, order, prim_ids, deep_cap, out_prims, out_dist, counts, counters3);
+    return walk_slice<float, LEAF_TRIANGLE>(pairs, root_index, prims, queries, first, n, launch_lanes, k, stride, order, prim_ids, deep_cap, out_prims, out_dist, counts, counters3);
 }
 
 } // extern "C"

@@ -41,6 +41,34 @@ int walk(const void* pairs, uint32_t root_index, const void* bboxes, const uint3
     return 0;
 }
 
+// One launch of a sliced batch as the device runs it (prelude: GuardedSpill, run_slice): the spill sized for the launch's lanes.
+template <typename T>
+long long walk_slice(const void* pairs, uint32_t root_index, const void* bboxes, const uint32_t* box_ids, const void* queries, size_t first, size_t n,
+                     size_t launch_lanes, const uint32_t* order, int original_ids, uint32_t deep_cap, uint32_t* counts, const uint64_t* offsets,
+                     uint32_t* list_prims, unsigned long long* counters3) {
+    if (deep_cap == 0 || n > launch_lanes) return kSliceBadArgs;
+    OverlapArgs<T> a{};
+    a.pairs = static_cast<const PairNode<T>*>(pairs); a.prims = static_cast<const T*>(bboxes); a.queries = static_cast<const T*>(queries);
+    a.box_ids = box_ids; a.counts = counts; a.offsets = reinterpret_cast<const unsigned long long*>(offsets); a.list_prims = list_prims;
+    a.n = n; a.first = first; a.order = order; a.prim_ids = original_ids ? box_ids : nullptr; a.counters = nullptr;
+    a.deep_cap = deep_cap; a.root_index = root_index;
+    GuardedSpill<uint32_t> deep_nodes(first, launch_lanes, deep_cap);
+    a.deep_nodes = deep_nodes.data();
+    std::vector<uint32_t> lds_node(size_t(kOverlapLds) * kBlock);
+    const bool self = queries == nullptr, fill = offsets != nullptr;
+    run_slice(n, kBlock, counters3, [&](unsigned long long lane, int tid, unsigned long long (&cnt)[3]) {
+        if (self) {
+            if (fill) overlap_lane<T, true, true, true, true>(a, first + lane, lds_node.data(), tid, lane, cnt);
+            else overlap_lane<T, true, true, false, true>(a, first + lane, lds_node.data(), tid, lane, cnt);
+        } else {
+            if (fill) overlap_lane<T, true, true, true, false>(a, first + lane, lds_node.data(), tid, lane, cnt);
+            else overlap_lane<T, true, true, false, false>(a, first + lane, lds_node.data(), tid, lane, cnt);
+        }
+    });
+    if (!deep_nodes.guards_intact()) return kSliceGuardBroken;
+    return deep_nodes.overwritten();
+}
+
 } // namespace
 
 extern "C" {
@@ -55,6 +83,18 @@ int overlap_host_walk(int is_double, const void* pairs, uint32_t root_index, con
                       uint32_t* list_prims, unsigned long long* counters3) {
     if (is_double) return walk<double>(pairs, root_index, bboxes, box_ids, queries, n, order, original_ids, deep_cap, threads, counts, offsets, list_prims, counters3);
     return walk<float>(pairs, root_index, bboxes, box_ids, queries, n, order, original_ids, deep_cap, threads, counts, offsets, list_prims, counters3);
+}
+
+// One launch of a batch that point_query_run cut into slices (deep_cap > 0): slots [first, first + n) as the device walks them —
+// a.first = first, slot = first + lane (in self mode: BVH-order primitive first + lane), lane = 0 .. n-1 indexing a spill of
+// launch_lanes * deep_cap entries that the launch's lanes share, tid = lane % 256 in one LDS stand-in. queries, order, counts, offsets
+// and the list are the whole batch's. Returns the spill entries the launch overwrote, -1 if a guard zone around the spill was written
+// to, -2 for deep_cap == 0 or n > launch_lanes.
+long long overlap_host_walk_slice(int is_double, const void* pairs, uint32_t root_index, const void* bboxes, const uint32_t* box_ids, const void* queries,
+                                  size_t first, size_t n, size_t launch_lanes, const uint32_t* order, int original_ids, uint32_t deep_cap, uint32_t* counts,
+                                  const uint64_t* offsets, uint32_t* list_prims, unsigned long long* counters3) {
+    if (is_double) return walk_slice<double>(pairs, root_index, bboxes, box_ids, queries, first, n, launch_lanes, order, original_ids, deep_cap, counts, offsets, list_prims, counters3);
+    return walk_slice<float>(pairs, root_index, bboxes, box_ids, queries, first, n, launch_lanes, order, original_ids, deep_cap, counts, offsets, list_prims, counters3);
 }
 
 } // extern "C"

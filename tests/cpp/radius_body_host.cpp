@@ -39,6 +39,28 @@ int walk(const void* pairs, uint32_t root_index, const void* prims, const void* 
     return 0;
 }
 
+// One launch of a sliced batch as the device runs it (prelude: GuardedSpill, run_slice): the spill sized for the launch's lanes.
+template <typename T, int Leaf>
+long long walk_slice(const void* pairs, uint32_t root_index, const void* prims, const void* queries, size_t first, size_t n, size_t launch_lanes,
+                     const uint32_t* order, const uint32_t* prim_ids, uint32_t deep_cap, uint32_t* counts, const uint64_t* offsets, uint32_t* list_prims,
+                     void* list_dist, unsigned long long* counters3) {
+    if (deep_cap == 0 || n > launch_lanes) return kSliceBadArgs;
+    RadiusArgs<T> a{};
+    a.pairs = static_cast<const PairNode<T>*>(pairs); a.prims = static_cast<const T*>(prims); a.queries = static_cast<const T*>(queries);
+    a.counts = counts; a.offsets = reinterpret_cast<const unsigned long long*>(offsets); a.list_prims = list_prims; a.list_dist = static_cast<T*>(list_dist);
+    a.n = n; a.first = first; a.order = order; a.prim_ids = prim_ids; a.counters = nullptr;
+    a.deep_cap = deep_cap; a.root_index = root_index;
+    GuardedSpill<uint32_t> deep_nodes(first, launch_lanes, deep_cap);
+    a.deep_nodes = deep_nodes.data();
+    std::vector<uint32_t> lds_node(size_t(kRadiusLds) * kBlock);
+    run_slice(n, kBlock, counters3, [&](unsigned long long lane, int tid, unsigned long long (&cnt)[3]) {
+        if (a.offsets) radius_lane<T, Leaf, true, true, true>(a, first + lane, lds_node.data(), tid, lane, cnt);
+        else radius_lane<T, Leaf, true, true, false>(a, first + lane, lds_node.data(), tid, lane, cnt);
+    });
+    if (!deep_nodes.guards_intact()) return kSliceGuardBroken;
+    return deep_nodes.overwritten();
+}
+
 template <typename T, int Leaf>
 T prim_dist2(const T* prims, size_t i, const T (&q)[3]) {
     T u = T(0), v = T(0);
@@ -90,6 +112,21 @@ int radius_host_walk(int is_double, int leaf, const void* pairs, uint32_t root_i
     }
     if (leaf == LEAF_SPHERE) return walk<float, LEAF_SPHERE>(pairs, root_index, prims, queries, n, order, prim_ids, deep_cap, threads, counts, offsets, list_prims, list_dist, counters3);
     return walk<float, LEAF_TRIANGLE>(pairs, root_index, prims, queries, n, order, prim_ids, deep_cap, threads, counts, offsets, list_prims, list_dist, counters3);
+}
+
+// One launch of a batch that point_query_run cut into slices (deep_cap > 0): slots [first, first + n) as the device walks them —
+// a.first = first, slot = first + lane, lane = 0 .. n-1 indexing a spill of launch_lanes * deep_cap entries that the launch's lanes
+// share, tid = lane % 256 in one LDS stand-in. queries, order, counts, offsets and the lists are the whole batch's. Returns the spill
+// entries the launch overwrote, -1 if a guard zone around the spill was written to, -2 for deep_cap == 0 or n > launch_lanes.
+long long radius_host_walk_slice(int is_double, int leaf, const void* pairs, uint32_t root_index, const void* prims, const void* queries, size_t first,
+                                 size_t n, size_t launch_lanes, const uint32_t* order, const uint32_t* prim_ids, uint32_t deep_cap, uint32_t* counts,
+                                 const uint64_t* offsets, uint32_t* list_prims, void* list_dist, unsigned long long* counters3) {
+    if (is_double) {
+        if (leaf == LEAF_SPHERE) return walk_slice<double, LEAF_SPHERE>(pairs, root_index, prims, queries, first, n, launch_lanes, order, prim_ids, deep_cap, counts, offsets, list_prims, list_dist, counters3);
+        return walk_slice<double, LEAF_TRIANGLE>(pairs, root_index, prims, queries, first, n, launch_lanes, order, prim_ids, deep_cap, counts, offsets, list_prims, list_dist, counters3);
+    }
+    if (leaf == LEAF_SPHERE) return walk_slice<float, LEAF_SPHERE>(pairs, root_index, prims, queries, first, n, launch_lanes, order, prim_ids, deep_cap, counts, offsets, list_prims, list_dist, counters3);
+    return walk_slice<float, LEAF_TRIANGLE>(pairs, root_index, prims, queries, first, n, launch_lanes, order, prim_ids, deep_cap, counts, offsets, list_prims, list_dist, counters3);
 }
 
 } // extern "C"
