@@ -588,7 +588,7 @@ int intersect_instanced(const typename Family<T, 3>::Bvh* top, const Geometry* g
 }
 
 // bvhXX_intersect_ray{,_any}{,_robust} (c_api/bvh.h:277-295 over bvh_impl.h:235-250): one ray, the leaves go to the caller's
-// function. The walk runs on the device (traverse.hip, ray_step_kernel); `ray` is the family's own struct.
+// function. The walk runs on the device (ray_callback.hip, ray_step_kernel); `ray` is the family's own struct.
 template <typename T, int D>
 int intersect_ray_visit(const BvhImpl<T>* b, const void* ray, size_t start, unsigned flags, bool (*leaf_fn)(void*, T*, size_t, size_t),
                         void (*inner_fn)(void*, size_t), void* user) {

@@ -309,7 +309,8 @@ int kernel_times(float* ms_out, size_t capacity, size_t* count_out);
 int reorder_times(float* ms_out, size_t capacity, size_t* count_out);
 template <typename T>
 int trace_ray_callbacks(const BvhImpl<T>& b, const T ray8[8], uint32_t start, bool any, bool robust,
-                        bool (*leaf_fn)(void*, T*, size_t, size_t), void (*inner_fn)(void*, size_t), void* user);
+                        bool (*leaf_fn)(void*, T*, size_t, size_t), void (*inner_fn)(void*, size_t), void* user);   // ray_callback.hip
+void set_step_events(int events);                             // ray_callback.hip: set_experiment's "step_events" of the calling thread (-1: default)
 
 // prep.hip
 template <typename T> int launch_tri_bounds(const T* d_tris9, size_t n, T* d_bb, T* d_cc, hipStream_t s);

@@ -2,11 +2,9 @@
 // centre) and the two-level walk of one ray — a top tree over instance boxes, and at an instance the ray carried into object space and
 // walked through that geometry's own tree. Kept as an include so that tests/cpp/instanced_body_host.cpp compiles the very same text
 // for the host (one emulated lane per ray / instance). Expects what point_walk.inc expects (trace_device.h: Num, dot3, load_pair,
-// load_prim12, load_ray, store_hit; common.h or the harnesses' stand-ins). The stack's tiers and index arithmetic are point_walk.inc's.
+// load_prim12, load_ray, store_hit; common.h or the harnesses' stand-ins). The stack's tiers and index arithmetic are point_walk.inc's;
+// the ray constants and the slab step are trace_device.h's (ray_constants, slab_pair), the triangle test is tri_test.inc: all shared with trace_body.inc.
 // Compiled with -ffp-contract=off on both sides: one rounding per operation, so host and device produce the same bits.
-//
-// trace_body.inc keeps its own copy of the ray constants and of the slab step (tests/test_trace_isa.py pins its instruction stream);
-// ray_constants / slab_pair below are the same arithmetic, operation for operation, as functions.
 #pragma once
 
 #include "point_walk.inc"
@@ -59,46 +57,11 @@ struct InstancedArgs {
     InstGeomTable<T, Small> geoms;
 };
 
-// bvh.h:162-165, ray.h:29-48: inverse direction, its padded form (robust) or -inv * org (fast), octant.
-template <typename T, bool Robust>
-__device__ inline void ray_constants(const T (&org)[3], const T (&dir)[3], T (&inv)[3], T (&aux)[3], uint32_t (&oct)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const T d = dir[k];
-        const T iv = Robust ? T(1) / d : (Num<T>::abs_(d) <= Num<T>::kEps ? Num<T>::copysign_(Num<T>::kMax, d) : T(1) / d);
-        inv[k] = iv;
-        aux[k] = Robust ? (Num<T>::finite(iv) ? Num<T>::bump2(iv) : iv) : (-iv) * org[k];
-        oct[k] = Num<T>::sign(d) ? 1u : 0u;
-    }
-}
-
-// node.h:74-75 / 85-86, 105-117: the entry and exit parameters of the ray in the two boxes of one record.
-template <typename T, bool Robust>
-__device__ inline void slab_pair(const T (&lb)[6], const T (&rb)[6], const T (&org)[3], const T (&inv)[3], const T (&aux)[3], const uint32_t (&oct)[3],
-                                 T tmin, T tmax, T& l0, T& l1, T& r0, T& r1) {
-    l0 = tmin; l1 = tmax; r0 = tmin; r1 = tmax;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const T ln = oct[k] ? lb[2 * k + 1] : lb[2 * k], lf = oct[k] ? lb[2 * k] : lb[2 * k + 1];
-        const T rn = oct[k] ? rb[2 * k + 1] : rb[2 * k], rf = oct[k] ? rb[2 * k] : rb[2 * k + 1];
-        T la, lz, ra, rz;
-        if (Robust) {
-            la = (ln - org[k]) * inv[k]; lz = (lf - org[k]) * aux[k];
-            ra = (rn - org[k]) * inv[k]; rz = (rf - org[k]) * aux[k];
-        } else {
-            la = Num<T>::fma_(ln, inv[k], aux[k]); lz = Num<T>::fma_(lf, inv[k], aux[k]);
-            ra = Num<T>::fma_(rn, inv[k], aux[k]); rz = Num<T>::fma_(rf, inv[k], aux[k]);
-        }
-        l0 = Num<T>::max_num(la, l0); l1 = Num<T>::min_num(lz, l1);
-        r0 = Num<T>::max_num(ra, r0); r1 = Num<T>::min_num(rz, r1);
-    }
-}
-
 // One ray, one lane. Walks the top tree as Bvh::intersect<Any, Robust> does (the root box is never tested, near child first and the
 // far one stacked, ties to the left, any-hit never reorders); at a top leaf takes its slots in order; an enabled instance with a
 // geometry of the table gets the ray in its object space (org' = W org + w, dir' = W dir through dot3, tmin and the current tmax as
 // they are: the direction is not normalised, so t means the same in both spaces), and its tree is walked from its root index word
-// with the same rules and trace_body.inc's triangle test. An accepted hit shortens tmax for everything after it, in both levels.
+// with the same rules and the batch kernels' triangle test. An accepted hit shortens tmax for everything after it, in both levels.
 //
 // One stack serves both levels: entering an instance pushes a marker — the rest of the top leaf as a leaf word, (next slot) << 4 |
 // slots left, possibly none — and the geometry's walk treats the stack height above it (`base`) as empty. Popping the marker restores
@@ -118,7 +81,7 @@ __device__ inline void instanced_lane(const InstancedArgs<T, Small>& a, unsigned
     const T tmin = r[6];
     T tmax = r[7];
     const bool nan_ray = !(tmin == tmin) || !(tmax == tmax);
-    ray_constants<T, Robust>(org, dir, inv, aux, oct);
+    ray_constants<T, Robust, 3>(org, dir, inv, aux, oct);
 
     uint32_t hit_prim = BVH_AMD_INVALID, hit_inst = BVH_AMD_INVALID;
     T hit_t = tmax, hit_u = T(0), hit_v = T(0);
@@ -150,7 +113,7 @@ __device__ inline void instanced_lane(const InstancedArgs<T, Small>& a, unsigned
             uint32_t li = 0, ri2 = 0;
             load_pair(pairs + (node >> (kCountBits + 1)), lb, rb, li, ri2);
             if (Stats) ++cnt[0];
-            slab_pair<T, Robust>(lb, rb, org, inv, aux, oct, tmin, tmax, l0, l1, r0, r1);
+            slab_pair<T, Robust, 3>(lb, rb, org, inv, aux, oct, tmin, tmax, l0, l1, r0, r1);
             const bool hl = l0 <= l1, hr = r0 <= r1;
             if (hl) {
                 uint32_t near_i = li;
@@ -179,17 +142,9 @@ __device__ inline void instanced_lane(const InstancedArgs<T, Small>& a, unsigned
                     if (Stats) ++cnt[1];
                     T p[12];
                     load_prim12(tris + 12ull * i, p);
-                    const T c0 = p[0] - org[0], c1 = p[1] - org[1], c2 = p[2] - org[2];
-                    const T rx = dir[1] * c2 - dir[2] * c1, ry = dir[2] * c0 - dir[0] * c2, rz = dir[0] * c1 - dir[1] * c0;
-                    const T inv_det = T(1) / dot3(p[9], p[10], p[11], dir[0], dir[1], dir[2]);
-                    const T u = dot3(rx, ry, rz, p[6], p[7], p[8]) * inv_det;
-                    const T v = dot3(rx, ry, rz, p[3], p[4], p[5]) * inv_det;
-                    const T w = T(1) - u - v;
-                    const T tol = -Num<T>::kEps;
-                    if (u >= tol && v >= tol && w >= tol) {
-                        const T t = dot3(p[9], p[10], p[11], c0, c1, c2) * inv_det;
-                        if (t >= tmin && t <= tmax) { tmax = t; hit_t = t; hit_u = u; hit_v = v; hit_prim = i; hit_inst = inst; }
-                    }
+#define BVH_TRI_ACCEPTED hit_prim = i; hit_inst = inst
+#include "tri_test.inc"
+#undef BVH_TRI_ACCEPTED
                 }
                 if (Any && hit_prim != BVH_AMD_INVALID) break;
                 if (sp == base) ended = true;
@@ -208,7 +163,7 @@ __device__ inline void instanced_lane(const InstancedArgs<T, Small>& a, unsigned
             pairs = a.top_pairs;
             load_ray(a.rays + 8 * ri, r);
             org[0] = r[0]; org[1] = r[1]; org[2] = r[2]; dir[0] = r[3]; dir[1] = r[4]; dir[2] = r[5];
-            ray_constants<T, Robust>(org, dir, inv, aux, oct);
+            ray_constants<T, Robust, 3>(org, dir, inv, aux, oct);
             at_top_leaf = true;
         }
         if (at_top_leaf) {
@@ -230,7 +185,7 @@ __device__ inline void instanced_lane(const InstancedArgs<T, Small>& a, unsigned
                     org[k] = dot3(w[4 * k], w[4 * k + 1], w[4 * k + 2], o0, o1, o2) + w[4 * k + 3];
                     dir[k] = dot3(w[4 * k], w[4 * k + 1], w[4 * k + 2], d0, d1, d2);
                 }
-                ray_constants<T, Robust>(org, dir, inv, aux, oct);
+                ray_constants<T, Robust, 3>(org, dir, inv, aux, oct);
                 pairs = a.geoms.g[gi].pairs;
                 tris = a.geoms.g[gi].tris;
                 node = a.geoms.g[gi].root_index;

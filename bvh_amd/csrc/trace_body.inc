@@ -111,15 +111,8 @@
                         r[0] = q[0]; r[1] = q[1]; r[2] = T(0); r[3] = q[2]; r[4] = q[3]; r[5] = T(0); r[6] = q[4]; r[7] = q[5];
                     }
 #pragma unroll
-                    for (int k = 0; k < D; ++k) {                       // bvh.h:162-165, ray.h:29-48
-                        org[k] = r[k]; dir[k] = r[3 + k];
-                        T d = dir[k];
-                        T iv = Robust ? T(1) / d
-                                      : (Num<T>::abs_(d) <= Num<T>::kEps ? Num<T>::copysign_(Num<T>::kMax, d) : T(1) / d);
-                        inv[k] = iv;
-                        aux[k] = Robust ? (Num<T>::finite(iv) ? Num<T>::bump2(iv) : iv) : (-iv) * org[k];
-                        oct[k] = Num<T>::sign(d) ? 1u : 0u;
-                    }
+                    for (int k = 0; k < D; ++k) { org[k] = r[k]; dir[k] = r[3 + k]; }
+                    ray_constants<T, Robust, D>(org, dir, inv, aux, oct);
                     tmin = r[6]; tmax = r[7];
                     nan_ray = !(tmin == tmin) || !(tmax == tmax);
                     ray_id = my;
@@ -160,26 +153,8 @@
             if (inner) {
                 if constexpr (!BVH_TRACE_COOP) load_pair(a.pairs + (top >> (kCountBits + 1)), lb, rb, li, ri);
                 if (Stats) ++n_pairs;
-                T l0 = tmin, l1 = tmax, r0 = tmin, r1 = tmax;               // node.h:105-117
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const T ln = oct[k] ? lb[2 * k + 1] : lb[2 * k], lf = oct[k] ? lb[2 * k] : lb[2 * k + 1];
-                    const T rn = oct[k] ? rb[2 * k + 1] : rb[2 * k], rf = oct[k] ? rb[2 * k] : rb[2 * k + 1];
-                    T la, lz, ra, rz;
-                    if (Robust) {                                           // node.h:74-75
-                        la = (ln - org[k]) * inv[k]; lz = (lf - org[k]) * aux[k];
-                        ra = (rn - org[k]) * inv[k]; rz = (rf - org[k]) * aux[k];
-                    } else {                                                // node.h:85-86
-                        la = Num<T>::fma_(ln, inv[k], aux[k]); lz = Num<T>::fma_(lf, inv[k], aux[k]);
-                        ra = Num<T>::fma_(rn, inv[k], aux[k]); rz = Num<T>::fma_(rf, inv[k], aux[k]);
-                    }
-                    // robust_max(la, l0) = la > l0 ? la : l0 (utils.h:41-43) lets l0 win when la is NaN, like the hardware's
-                    // max; the two differ only when l0 itself is NaN, which takes a NaN tmin / tmax of the ray (a computed
-                    // operand never replaces the accumulator unless it compares greater): nan_ray below. One instruction
-                    // instead of compare + select, twelve times per step.
-                    l0 = Num<T>::max_num(la, l0); l1 = Num<T>::min_num(lz, l1);
-                    r0 = Num<T>::max_num(ra, r0); r1 = Num<T>::min_num(rz, r1);
-                }
+                T l0, l1, r0, r1;
+                slab_pair<T, Robust, D>(lb, rb, org, inv, aux, oct, tmin, tmax, l0, l1, r0, r1);
                 const bool hl = !nan_ray && l0 <= l1, hr = !nan_ray && r0 <= r1;   // bvh.h:177-180 (a NaN bound fails every test)
                 if (hl) {
                     uint32_t near_i = li;
@@ -210,17 +185,9 @@
                     // (loading the TRIANGLES non-temporally as well was measured and costs 23-35 %: neighbouring rays share them through the L2;
                     //  profiles/r04_experiments_call4_hints.txt)
                     load_prim12(a.prims + static_cast<unsigned long long>(a.prim_stride) * i, p);
-                    const T c0 = p[0] - org[0], c1 = p[1] - org[1], c2 = p[2] - org[2];
-                    const T rx = dir[1] * c2 - dir[2] * c1, ry = dir[2] * c0 - dir[0] * c2, rz = dir[0] * c1 - dir[1] * c0;
-                    const T inv_det = T(1) / dot3(p[9], p[10], p[11], dir[0], dir[1], dir[2]);
-                    const T u = dot3(rx, ry, rz, p[6], p[7], p[8]) * inv_det;
-                    const T v = dot3(rx, ry, rz, p[3], p[4], p[5]) * inv_det;
-                    const T w = T(1) - u - v;
-                    const T tol = -Num<T>::kEps;
-                    if (u >= tol && v >= tol && w >= tol) {
-                        const T t = dot3(p[9], p[10], p[11], c0, c1, c2) * inv_det;
-                        if (t >= tmin && t <= tmax) { tmax = t; hit_t = t; hit_u = u; hit_v = v; hit_prim = i; }
-                    }
+#define BVH_TRI_ACCEPTED hit_prim = i
+#include "tri_test.inc"
+#undef BVH_TRI_ACCEPTED
                 } else {                                                // sphere.h:32-49
                     T qa, qb, qc;
                     if (D == 3) {

@@ -1,6 +1,8 @@
 // Device-side helpers of the batch traversal kernels (traverse.hip): per-type arithmetic, record / ray / primitive loads, the
-// kernel argument block. Kept apart from traverse.hip so that tests/cpp/trace_body_host.cpp can compile the kernel BODY
-// (trace_body.inc) for the host with one emulated lane (test infrastructure; the product only ever runs it on the device).
+// kernel argument block — and the one copy of the ray arithmetic (ray_constants, slab_pair) that the batch kernels, the instanced
+// walk (instanced_body.inc) and the per-ray callback walk (ray_callback.hip) all call; the triangle test is tri_test.inc. Kept apart from traverse.hip so
+// that tests/cpp/trace_body_host.cpp can compile the kernel BODY (trace_body.inc) for the host with one emulated lane (test
+// infrastructure; the product only ever runs it on the device).
 // Expects common.h (or the test's stand-ins for it) to have been included: PairNode, HitOf, kCountBits, kCountMask, kWave, LEAF_*.
 #pragma once
 
@@ -81,6 +83,46 @@ __device__ inline uint32_t lds_word(const uint32_t* shared) {
 }
 
 template <typename T> __device__ inline T dot2(T a0, T a1, T b0, T b1) { return (T(0) + a0 * b0) + a1 * b1; }   // Vec<T, 2>
+
+// ---- the ray arithmetic every ray walk shares (trace_body.inc, instanced_body.inc, ray_callback.hip) -------------------------------
+// bvh.h:162-165, ray.h:29-48: inverse direction, its padded form (robust) or -inv * org (fast), octant; over the first D axes.
+template <typename T, bool Robust, int D>
+__device__ inline void ray_constants(const T (&org)[3], const T (&dir)[3], T (&inv)[3], T (&aux)[3], uint32_t (&oct)[3]) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const T d = dir[k];
+        const T iv = Robust ? T(1) / d : (Num<T>::abs_(d) <= Num<T>::kEps ? Num<T>::copysign_(Num<T>::kMax, d) : T(1) / d);
+        inv[k] = iv;
+        aux[k] = Robust ? (Num<T>::finite(iv) ? Num<T>::bump2(iv) : iv) : (-iv) * org[k];
+        oct[k] = Num<T>::sign(d) ? 1u : 0u;
+    }
+}
+
+// node.h:74-75 / 85-86, 105-117: the entry and exit parameters of the ray in the two boxes of one record, over the first D axes.
+// robust_max(la, l0) = la > l0 ? la : l0 (utils.h:41-43) lets l0 win when la is NaN, like the hardware's max; the two differ only
+// when l0 itself is NaN, which takes a NaN tmin / tmax of the ray (a computed operand never replaces the accumulator unless it
+// compares greater). The CALLER therefore fails both box tests of a ray whose tmin or tmax is NaN (`nan_ray`), or never walks it.
+// One instruction instead of compare + select, twelve times per step.
+template <typename T, bool Robust, int D>
+__device__ inline void slab_pair(const T (&lb)[6], const T (&rb)[6], const T (&org)[3], const T (&inv)[3], const T (&aux)[3], const uint32_t (&oct)[3],
+                                 T tmin, T tmax, T& l0, T& l1, T& r0, T& r1) {
+    l0 = tmin; l1 = tmax; r0 = tmin; r1 = tmax;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const T ln = oct[k] ? lb[2 * k + 1] : lb[2 * k], lf = oct[k] ? lb[2 * k] : lb[2 * k + 1];
+        const T rn = oct[k] ? rb[2 * k + 1] : rb[2 * k], rf = oct[k] ? rb[2 * k] : rb[2 * k + 1];
+        T la, lz, ra, rz;
+        if (Robust) {
+            la = (ln - org[k]) * inv[k]; lz = (lf - org[k]) * aux[k];
+            ra = (rn - org[k]) * inv[k]; rz = (rf - org[k]) * aux[k];
+        } else {
+            la = Num<T>::fma_(ln, inv[k], aux[k]); lz = Num<T>::fma_(lf, inv[k], aux[k]);
+            ra = Num<T>::fma_(rn, inv[k], aux[k]); rz = Num<T>::fma_(rf, inv[k], aux[k]);
+        }
+        l0 = Num<T>::max_num(la, l0); l1 = Num<T>::min_num(lz, l1);
+        r0 = Num<T>::max_num(ra, r0); r1 = Num<T>::min_num(rz, r1);
+    }
+}
 
 constexpr uint32_t kTicketStride = 16;       // ticket counters 128 bytes apart
 

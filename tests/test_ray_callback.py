@@ -1,5 +1,5 @@
 """The reference's per-ray entry points with a HOST leaf callback (c_api/bvh.h:277-295, Bvh::intersect of bvh.h:160-182) served by
-the device walk of traverse.hip (ray_step_kernel), and the reference's own four example programs compiled unmodified against
+the device walk of ray_callback.hip (ray_step_kernel), and the reference's own four example programs compiled unmodified against
 this repo's headers ("must compile/link unmodified").
 
 CPU part: everything compiles and links; without a GPU the programs fail loudly. GPU part: results equal the oracle's, and
@@ -73,10 +73,35 @@ CASES = [("3f", "closest", 0, 1), ("3f", "closest", 1, 1), ("3f", "any", 0, 1), 
          ("3f", "closest", 1, 8), ("2d", "any", 0, 5)]          # several host threads through one bvh
 
 
+def _oracle_walk(orc, family, prims, rays, any_hit, robust):
+    """The oracle's tree as tests/c/ray_callback.c builds it, its hit records for `rays` and its counters."""
+    import oracle
+    if family[0] == "3":
+        bb, cc = orc.prep_tris(prims)
+        ob = orc.build(bb, cc, builder=oracle.BUILDER_DEFAULT_PARALLEL, quality=oracle.QUALITY_HIGH)        # bvh3X_build(pool, ..., NULL)
+        want, cnt = ob.intersect_tri(orc.precompute_tris(prims, ob.prim_ids()), rays, any_hit, robust, counters=True)
+    else:
+        bb, cc = orc.sphere_bboxes(prims)
+        ob = orc.build(bb, cc, quality=oracle.QUALITY_HIGH)                                                 # bvh2X_build(NULL, ..., NULL)
+        want, cnt = ob.intersect_sphere(prims[ob.prim_ids().astype(np.int64)], rays, any_hit, robust, counters=True)
+    return ob, want, cnt
+
+
+def _run_callbacks(exe, tmp_path, family, mode, robust, threads, prims, rays):
+    """tests/c/ray_callback.c on these rays: per ray {original primitive id or -1, t}, and the leaf callbacks made in total."""
+    m = len(rays)
+    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
+    inp.write_bytes(np.array([len(prims), m], dtype=np.uint64).tobytes() + prims.tobytes() + rays.tobytes())
+    r = subprocess.run([exe, family, mode, str(robust), str(inp), str(outp), str(threads)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    raw = outp.read_bytes()
+    got = np.frombuffer(raw[:16 * m], dtype=[("prim", "<i8"), ("t", "<f8")])
+    return got, int(np.frombuffer(raw[16 * m:], dtype="<u8")[0])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("family,mode,robust,threads", CASES)
 def test_c_callback_api_matches_oracle(tmp_path, orc, family, mode, robust, threads):
-    import oracle
     exe = _compile_c(str(tmp_path / "ray_callback"))
     dt = np.float32 if family[1] == "f" else np.float64
     any_hit = mode == "any"
@@ -85,22 +110,11 @@ def test_c_callback_api_matches_oracle(tmp_path, orc, family, mode, robust, thre
         prims = synth.sponza_proxy(20000).astype(dt)
         lo, hi = synth.scene_bounds(prims)
         rays = (synth.rays_shadow(m, lo, hi) if any_hit else synth.rays_closest(m, lo, hi)).astype(dt)
-        bb, cc = orc.prep_tris(prims)
-        ob = orc.build(bb, cc, builder=oracle.BUILDER_DEFAULT_PARALLEL, quality=oracle.QUALITY_HIGH)        # bvh3X_build(pool, ..., NULL)
-        want, cnt = ob.intersect_tri(orc.precompute_tris(prims, ob.prim_ids()), rays, any_hit, robust, counters=True)
     else:
         prims = synth.circles(4000, dtype=dt)
         rays = synth.rays_2d(m, dtype=dt, segment=any_hit)
-        bb, cc = orc.sphere_bboxes(prims)
-        ob = orc.build(bb, cc, quality=oracle.QUALITY_HIGH)                                                 # bvh2X_build(NULL, ..., NULL)
-        want, cnt = ob.intersect_sphere(prims[ob.prim_ids().astype(np.int64)], rays, any_hit, robust, counters=True)
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    inp.write_bytes(np.array([len(prims), m], dtype=np.uint64).tobytes() + prims.tobytes() + rays.tobytes())
-    r = subprocess.run([exe, family, mode, str(robust), str(inp), str(outp), str(threads)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    raw = outp.read_bytes()
-    got = np.frombuffer(raw[:16 * m], dtype=[("prim", "<i8"), ("t", "<f8")])
-    calls = int(np.frombuffer(raw[16 * m:], dtype="<u8")[0])
+    ob, want, cnt = _oracle_walk(orc, family, prims, rays, any_hit, robust)
+    got, calls = _run_callbacks(exe, tmp_path, family, mode, robust, threads, prims, rays)
     ids = ob.prim_ids().astype(np.int64)
     hit = want["prim"] != 0xFFFFFFFF
     want_prim = np.where(hit, ids[np.minimum(want["prim"], len(ids) - 1)], -1)
@@ -109,6 +123,51 @@ def test_c_callback_api_matches_oracle(tmp_path, orc, family, mode, robust, thre
     assert (got["t"][hit] == want["t"][hit].astype(np.float64)).all()          # bit-exact t (the parity bar is 1e-5)
     assert (got["t"][~hit] == rays[~hit, -1].astype(np.float64)).all()         # a miss leaves tmax alone
     assert calls == int(cnt[2])                               # one callback per leaf the reference visits: same walk, same culling
+
+
+def _nan_ray_batch(family, dt):
+    """A 64-primitive scene, 16 ordinary rays, then 8 rays with a NaN in them: tmin, tmax, both (the NaN-RANGE rays: they fail every
+    box test there is), or one direction component (a NaN operand of the slab test, which loses to the bound it is compared with)."""
+    nan = np.nan
+    if family[0] == "3":
+        prims = synth.soup(64, jitter=0.2).astype(dt)
+        lo, hi = synth.scene_bounds(prims)
+        rays = synth.rays_closest(24, lo, hi).astype(dt)
+        first_dir = 3
+    else:
+        prims = synth.circles(64, rmin=0.03, rmax=0.08, dtype=dt)
+        rays = synth.rays_2d(24, dtype=dt)
+        first_dir = 2
+    rays[16:18, -2] = nan
+    rays[18:20, -1] = nan
+    rays[20:22, -2:] = nan
+    rays[22, first_dir] = nan
+    rays[23, first_dir + 1] = nan
+    return prims, rays, slice(16, 22)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robust", [0, 1])
+@pytest.mark.parametrize("family", ["3f", "2d"])
+def test_c_callback_api_nan_rays_match_oracle(tmp_path, orc, family, robust):
+    """Rays with a NaN tmin / tmax / direction component through the per-ray entry points: the records and the leaf callbacks are the
+    oracle's, and a NaN-range ray is a miss that reaches no leaf (ray_step_kernel fails its box tests by a guard, not by arithmetic)."""
+    exe = _compile_c(str(tmp_path / "ray_callback"))
+    dt = np.float32 if family[1] == "f" else np.float64
+    prims, rays, nan_range = _nan_ray_batch(family, dt)
+    ob, want, cnt = _oracle_walk(orc, family, prims, rays, False, robust)
+    _, want_nan, cnt_nan = _oracle_walk(orc, family, prims, rays[nan_range], False, robust)
+    assert (want_nan["prim"] == 0xFFFFFFFF).all() and int(cnt_nan[2]) == 0          # what the oracle does with them
+    got, calls = _run_callbacks(exe, tmp_path, family, "closest", robust, 1, prims, rays)
+    ids = ob.prim_ids().astype(np.int64)
+    hit = want["prim"] != 0xFFFFFFFF
+    assert hit[:16].any() and not hit[16:22].any()
+    assert (got["prim"] == np.where(hit, ids[np.minimum(want["prim"], len(ids) - 1)], -1)).all()
+    assert (got["t"][hit] == want["t"][hit].astype(np.float64)).all()
+    assert np.array_equal(got["t"][~hit], rays[~hit, -1].astype(np.float64), equal_nan=True)   # a miss leaves tmax alone, a NaN one too
+    assert calls == int(cnt[2])
+    got_nan, calls_nan = _run_callbacks(exe, tmp_path, family, "closest", robust, 1, prims, rays[nan_range])
+    assert (got_nan["prim"] == -1).all() and calls_nan == 0
 
 
 @pytest.mark.gpu
