@@ -21,10 +21,25 @@ namespace {
 // select the XCD's ticket range), the chord class of the ray, longest class first, and the cell index gives up its lowest `class_bits`
 // bits (neighbours along the curve merge): every XCD still sweeps its part of space in curve order, once per class, and the tickets
 // drawn last are the short rays. Per-ray results do not depend on the order.
+// `tail_frac` >= 0 with class_bits == 1 — A TAIL CLASS: the order inside every prefix is long / short / TAIL. Tail rays are those whose
+// chord through the root box is not longer than tail_frac box diagonals: with 0 the rays that have no chord at all (they miss the box, or
+// their [tmin, tmax] is empty: one step, no record fetch), with 0.05 also the ~10 % of a uniform batch that walk a third as far as the
+// short class's longest. They are what an XCD should hold when its range runs out: cheap, and numerous enough to keep the machine busy
+// while the last real walks finish. The class takes two bits of the key (0 long, 1 short, 2 tail) and the cell index gives up two low
+// bits instead of one: [3 prefix bits][2 class bits][cell bits - 2][3 octant bits]. The ticket range of an XCD is the stretch of one
+// prefix (traverse.hip: ticket_ranges_kernel), so "last in the prefix" is "last in the range".
+// Degenerate rays land in defined classes (tests/test_ticket_ranges_host.py): a NaN origin component clips nothing along its axis (the
+// comparisons are false) and counts as cell 0; a NaN or all-zero direction gives a NaN or zero length: not long, hence — with a tail
+// class — tail; a NaN tmin / tmax gives no chord (nothing compares greater than it): tail as well.
+#if defined(__HIPCC__)
 __device__ inline float rcp_fast(float x) { return __builtin_amdgcn_rcpf(x); }       // v_rcp_f32; ordering keys only
+#else
+inline float rcp_fast(float x) { return 1.0f / x; }                                   // (the host harness of tests/cpp/ticket_ranges_host.cpp)
+#endif
 __device__ inline double rcp_fast(double x) { return 1.0 / x; }
 template <typename T>
-__device__ inline uint32_t ray_key(const T (&r)[8], T lx, T ly, T lz, T sx, T sy, T sz, uint32_t cells, int hilbert_bits, int class_bits, T class_scale) {
+__device__ inline uint32_t ray_key(const T (&r)[8], T lx, T ly, T lz, T sx, T sy, T sz, uint32_t cells, int hilbert_bits, int class_bits, T class_scale,
+                                   T tail_frac = T(-1)) {
     const T q[3] = { (r[0] - lx) * sx, (r[1] - ly) * sy, (r[2] - lz) * sz };
     uint32_t code = 0;
     uint32_t cell[3];
@@ -76,16 +91,23 @@ __device__ inline uint32_t ray_key(const T (&r)[8], T lx, T ly, T lz, T sx, T sy
         }
         const uint32_t top = (1u << class_bits) - 1u;
         uint32_t cls = 0;
+        int field_bits = class_bits;                                    // bits of the key the class takes from the cell index
         const T len = t1 > t0 ? t1 - t0 : T(0);
-        if (class_bits == 1) cls = len * len * d2 * class_scale * class_scale >= diag2 && diag2 > T(0) ? 1u : 0u;
-        else {
+        if (class_bits == 1) {
+            const T len2 = len * len * d2;                              // the squared chord
+            cls = len2 * class_scale * class_scale >= diag2 && diag2 > T(0) ? 0u : 1u;      // long / short
+            if (tail_frac >= T(0)) {
+                if (cls != 0u && !(len2 > tail_frac * tail_frac * diag2)) cls = 2u;         // tail (no chord at all, a NaN length included)
+                field_bits = 2;
+            }
+        } else {
             const T rel = diag2 > T(0) ? len * Num<T>::sqrt_(d2) / Num<T>::sqrt_(diag2) * class_scale : T(0);
             cls = rel >= T(top) ? top : rel > T(0) ? static_cast<uint32_t>(rel) : 0u;
+            cls = top - cls;                                            // longest class first
         }
-        cls = top - cls;                                                // longest class first
         const int code_bits = 3 * (hilbert_bits > 0 ? hilbert_bits : 31 - __clz(cells));
-        const uint32_t high = code >> (code_bits - 3), low = (code & ((1u << (code_bits - 3)) - 1u)) >> class_bits;
-        code = (((high << class_bits) | cls) << (code_bits - 3 - class_bits)) | low;
+        const uint32_t high = code >> (code_bits - 3), low = (code & ((1u << (code_bits - 3)) - 1u)) >> field_bits;
+        code = (((high << field_bits) | cls) << (code_bits - 3 - field_bits)) | low;
     }
     return (code << 3) | oct;
 }

@@ -20,6 +20,9 @@
     // the next range when one runs dry. With coherence-sorted rays each L2 then serves one stretch of the order instead of
     // one eighth of every stretch (measured, 16M sorted rays on the 1M soup: 9.84 -> 9.62 ms; 4M rays on the 262k-triangle
     // Sponza proxy: 1.11 -> 0.76 ms. More ranges than XCDs lose again: 32 -> 9.66 ms, 512 -> 10.3 ms).
+    // The ranges are equal slices of the tickets, or, where the launch gives a.range_starts, the stretches of the sorted order that
+    // hold one key prefix each (ray_key.h): a range then ends on its own prefix's cheapest rays, not on the first — long — rays of the
+    // next prefix. The staggered drain below counts what is left up to the range's real end either way.
     uint32_t part = a.parts > 1 ? blockIdx.x % a.parts : 0, parts_left = a.parts;
     // (Reserving several refills' worth of tickets per atomic was measured and lost everywhere: a reservation that ends inside
     //  a refill leaves lanes idle, and waves sitting on reservations widen the stretch of the order in flight.)
@@ -84,8 +87,13 @@
                 drained = true;
             } else {
                 if (lane == 0) base = atomicAdd(a.work + part * kTicketStride, static_cast<unsigned long long>(n_idle));
-                base = __shfl(base, 0) + part * a.part_size;
+                // the range's first ticket and its end: an equal slice, or — a reordered launch — the stretch of the order that holds one
+                // key prefix (a.range_starts, written on the device after the sort; any length, also none at all). Read here, in the
+                // refill branch, every time: nothing about a range stays live in the inner-node loop.
+                unsigned long long part_begin = part * a.part_size;
                 part_end = min(a.n, (part + 1ull) * a.part_size);
+                if (a.range_starts) { part_begin = a.range_starts[part]; part_end = a.range_starts[part + 1]; }
+                base = __shfl(base, 0) + part_begin;
                 if (base + n_idle >= part_end) {                     // this range is used up: the next one, or nothing left at all
                     part = part + 1 == a.parts ? 0 : part + 1;
                     if (--parts_left == 0) drained = true;

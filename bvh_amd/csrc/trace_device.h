@@ -134,7 +134,7 @@ struct TraceArgs {
     typename HitOf<T>::Type* hits;
     unsigned long long n;
     unsigned long long* work;                  // next ray ticket of part p of this launch at work[p * kTicketStride]
-    unsigned long long part_size;              // tickets [p * part_size, min(n, (p + 1) * part_size)) form part p (a multiple of 64)
+    unsigned long long part_size;              // tickets [p * part_size, min(n, (p + 1) * part_size)) form part p (a multiple of 64) unless range_starts is given
     uint32_t parts;                            // 1, or one part per XCD (see trace_body.inc: refill)
     bvh_amd_counters* counters;
     const uint32_t* order;                     // optional: ticket -> ray index (coherence sort); results are unaffected
@@ -151,6 +151,8 @@ struct TraceArgs {
     unsigned long long* wave_times;            // developer library only (bvh_amd_experiment("wave_times", 1)): per wave {begin, last refill, end, xcc | rays, ticks inside refills, refills} in
                                                // s_memrealtime ticks (100 MHz) + {XCC id, rays traced}; nullptr otherwise — the release kernels never read it
     uint32_t pair_bytes = 0;                   // bytes of `pairs`: the size of the cooperative fetch's buffer descriptor (device only)
+    const uint32_t* range_starts = nullptr;    // optional, parts + 1 words in device memory: tickets [range_starts[p], range_starts[p + 1]) form part p instead of
+                                               // the equal slice (a reordered launch: one key prefix per XCD, traverse.hip: ticket_ranges_kernel)
 };
 
 __device__ inline void load_pair(const PairNode<float>* p, float (&lb)[6], float (&rb)[6], uint32_t& li, uint32_t& ri) {

@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(256) k_check_order(const uint32_t* order, uint
 
 template <typename T>
 __global__ void __launch_bounds__(1024) ray_keys_kernel(const T* rays, uint32_t n, T lx, T ly, T lz, T sx, T sy, T sz, uint32_t* keys, uint32_t cells,
-                                                        int hilbert_bits, int class_bits, T class_scale, uint32_t* hist, uint32_t tiles) {
+                                                        int hilbert_bits, int class_bits, T class_scale, T tail_frac, uint32_t* hist, uint32_t tiles) {
     __shared__ uint32_t h[256];
     if (threadIdx.x < 256) h[threadIdx.x] = 0;
     __syncthreads();
@@ -135,13 +135,37 @@ __global__ void __launch_bounds__(1024) ray_keys_kernel(const T* rays, uint32_t 
         if (i < n) {
             T r[8];
             load_ray_nt(rays + 8ull * i, r);
-            const uint32_t key = ray_key<T>(r, lx, ly, lz, sx, sy, sz, cells, hilbert_bits, class_bits, class_scale);
+            const uint32_t key = ray_key<T>(r, lx, ly, lz, sx, sy, sz, cells, hilbert_bits, class_bits, class_scale, tail_frac);
             keys[i] = key;
             atomicAdd(&h[key & 0xFFu], 1u);
         }
     }
     __syncthreads();
     if (threadIdx.x < 256) hist[size_t{threadIdx.x} * tiles + blockIdx.x] = h[threadIdx.x];   // digit-major, tile-minor: k_radix_hist's layout (sort_emul.hip)
+}
+
+// The ticket ranges of a reordered launch, one per XCD, written on the device once the sort has run (one small block; no host
+// synchronisation): range p = the stretch of the sorted order whose keys have the top-three-bit prefix p. `hist` is the sort's
+// scanned histogram of its LAST pass (sort_emul.hip: digit-major, tile-minor, exclusive), so hist[d * tiles] is the first position of
+// digit d and prefix p starts at digit p * digits_per_prefix. With equal slices the last 600-2900 tickets of about half of the
+// ranges were the first — LONG — rays of the next prefix (the prefixes of a uniform batch hold n / 8 +- a few thousand rays), and the
+// drain of the grid is as long as the longest walk drawn last; with the prefix's own stretch a range ends on its prefix's tail class
+// (ray_key.h). A skewed batch — all origins in one cell, a camera — must not funnel every XCD onto one counter (a single counter
+// costs 2x and more): the prefix boundaries are kept only when EVERY prefix holds between 3/4 and 5/4 of n / parts tickets, otherwise
+// the starts written are the equal slices. The same block zeroes the ticket counters, in place of the launch's memset.
+__global__ void __launch_bounds__(64) ticket_ranges_kernel(const uint32_t* hist, uint32_t tiles, uint32_t digits_per_prefix, uint32_t n, uint32_t parts,
+                                                           unsigned long long part_size, uint32_t* starts, unsigned long long* work) {
+    const uint32_t p = threadIdx.x;                           // parts <= 32 (launch_planned)
+    uint32_t begin = n, end = n;
+    if (p < parts) {
+        begin = hist[size_t{p} * digits_per_prefix * tiles];
+        if (p + 1 < parts) end = hist[size_t{p + 1} * digits_per_prefix * tiles];
+    }
+    const uint32_t even = n / parts, len = end - begin;
+    const bool balanced = p >= parts || (begin <= end && end <= n && 4ull * len >= 3ull * even && 4ull * len <= 5ull * even);
+    const bool keep = __ballot(!balanced) == 0;
+    if (p <= parts) starts[p] = keep ? begin : static_cast<uint32_t>(min(static_cast<unsigned long long>(n), p * part_size));
+    if (p < parts) work[p * kTicketStride] = 0;
 }
 
 // Developer experiment (BVH_AMD_RAY_KEY_DEPTH=k; profiles/r03_traversal_experiments.md §6): a TREE-ENTRY key — the ray descends the
@@ -200,13 +224,23 @@ thread_local int t_refill = -1, t_leaf = -1, t_coop = -1, t_parts = -1;
 //   wave_times    (developer library only) 1: the next launches record per-wave begin / last-refill / end timestamps (bvh_amd_wave_times)
 //   one_shot      1 / 0: force / forbid the one-shot grid of small batches (default: launch_planned decides by batch size)
 //   key_class_bits / key_class_scale   chord classes of the reordering key (0 = none) / classes per 100 box diagonals (ray_keys_kernel)
+//   key_tail / key_tail_permille       tail class of the one-bit key (ray_key.h) off / on, and its threshold in 1/1000 box diagonals
+//                                      (0: only rays with no chord through the root box at all)
+//   range_align   0: the ticket ranges of a reordered launch are equal slices, not the stretches of one key prefix each (ticket_ranges_kernel)
 struct Experiments { int grid_blocks = -1, stream_hints = -1, tri_stride = -1, key_curve = -1, key_bits = -1, wave_times = -1, one_shot = -1,
-                     key_class_bits = -1, key_class_scale = -1, stagger = -1; };
+                     key_class_bits = -1, key_class_scale = -1, stagger = -1, key_tail = -1, key_tail_permille = -1, range_align = -1; };
 // Round-5 measurements (profiles/r05_key_class_ab.txt, r05_stagger_ab.txt; 2^24 rays, kernel ms): 1M soup 6.92 without classes, one class bit
 // 6.99 / 6.80 / 6.76 / 6.70 / 6.64 at 2 / 2.5 / 3 / 4 / 5 classes per diagonal (only the shortest chords go last), two bits 6.80-6.84, three
 // 6.91-6.95; the 10M soup LOSES 6 % with any of them (83 % of its rays end at a hit long before their chord does: the chord predicts nothing
 // there, and two sweeps cost coherence) — so the classes are not a default but one more candidate of the measured plan search.
 constexpr int kKeyClassBits = 0, kKeyClassScalePercent = 500;
+// The tail class of the one-bit key (ray_key.h) and its threshold in 1/1000 box diagonals; the prefix-aligned ticket ranges (ticket_ranges_kernel).
+// Measured (profiles/r08_range_tail_sweep.jsonl; 1M soup, 2^24 rays, four rotating batches, pass ms = keys + sort + kernel, mean of two
+// rounds of 12 passes): equal slices without a tail class 6.93; aligned ranges alone 6.83; a tail class alone (equal slices) 6.97 — the tail
+// only pays where the range ends on it; both, by threshold x stagger {0, 50k, 100k, 170k}: chord-less rays only 6.86 / 6.85 / 6.81 / 6.84,
+// 0.025 diagonals 6.73 / 6.71 / 6.67 / 6.69, 0.05 diagonals 6.60 / 6.58 / 6.57 / 6.59, 0.1 diagonals 6.68 / 6.64 / 6.65 / 6.62.
+// So: 0.05 diagonals, and the stagger stays at 100k (50k-170k are within the +-0.02 ms the rounds differ by; none at all costs 0.03).
+constexpr int kKeyTail = 1, kKeyTailPermille = 50, kRangeAlign = 1;
 // Staggered drain (trace_body.inc), tickets per eighth of the grid: kernel ms against it — 1M soup 2^24 rays 7.03 / 6.93 / 6.90 / 7.17 at
 // 0 / 84k / 168k / 262k (with the chord classes 6.74 / 6.60 / 6.81 / 6.97), 2^22 rays 2.57 -> 2.46 at 131k, 10M soup 12.5M rays 5.50 -> 5.46
 // at 125k; light trees want less: Sponza proxy 1M rays 0.264 -> 0.236 at 44k (configs[1]: 3.7 -> 4.0 Grays/s), 4M rays 0.628 -> 0.597 at 42k,
@@ -369,6 +403,9 @@ int set_experiment(const char* name, int value) {
     else if (k == "stagger") t_exp.stagger = value;
     else if (k == "key_class_bits") t_exp.key_class_bits = value;
     else if (k == "key_class_scale") t_exp.key_class_scale = value;
+    else if (k == "key_tail") t_exp.key_tail = value;
+    else if (k == "key_tail_permille") t_exp.key_tail_permille = value;
+    else if (k == "range_align") t_exp.range_align = value;
     else if (k == "wave_times") {
 #if defined(BVH_AMD_DEVELOPER)
         t_exp.wave_times = value;
@@ -596,12 +633,14 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
     // eight counters then cost measurable time in atomics on one address each — 32 ranges (four per XCD) take the 1M terrain from 1.18
     // to 1.10 ms (per lane) and 1.31 to 1.12 ms (cooperative), the Sponza proxy's shadow rays from 1.63 to 1.52 ms; the sorted soup
     // prefers 8 (7.24 against 7.32 ms at 32); a single counter costs 2x and more (profiles/r03_traversal_experiments.md).
+    // The eight ranges of a reordered batch are not equal slices but the stretches of the eight key prefixes, where those are balanced
+    // (ticket_ranges_kernel, launched below once the sort has run: it writes args.range_starts and zeroes the counters).
     args.parts = t_parts > 0 ? std::min(t_parts, 256) : parts_env > 0 ? std::min(parts_env, 256) : n < 65536 ? 1 : g_last_reordered ? 8 : 32;
     args.part_size = ((n + args.parts - 1) / args.parts + 63) / 64 * 64;
-    if (const int rc0 = zero_tickets()) return release(rc0);
+    constexpr size_t kRangeWords = 64;                        // the range starts of a reordered launch live behind the sort's scratch
     if (g_last_reordered) {
         const uint32_t n32 = static_cast<uint32_t>(n);
-        const size_t words = 4 * n + radix_sort_hist_words(n32, 1);              // keys + tmp, indices + tmp, histogram
+        const size_t words = 4 * n + radix_sort_hist_words(n32, 1) + kRangeWords;   // keys + tmp, indices + tmp, histogram, range starts
         // (from the per-stream block cache the builders use: a stream-ordered allocation per call cost ~20 us of every timed pass)
         hipError_t e = scratch_alloc(&sort_mem, words * sizeof(uint32_t), &sort_tag);
         if (e != hipSuccess) {
@@ -611,7 +650,9 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
             g_last_reordered = false;                         // the reordering was this library's own idea: trace the rays as given instead
         }
     }
-    if (g_last_reordered) {
+    if (!g_last_reordered) {
+        if (const int rc0 = zero_tickets()) return release(rc0);
+    } else {
         const uint32_t n32 = static_cast<uint32_t>(n);
         uint32_t *keys = static_cast<uint32_t*>(sort_mem), *vals = keys + n, *kt = vals + n, *vt = kt + n, *hist = vt + n;
         T lo[3], sc[3];
@@ -638,10 +679,14 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
             const int class_bits = cell_bits < 3 ? 0 : t_exp.key_class_bits >= 0 ? std::min(3, t_exp.key_class_bits) : (plan && plan->classes) ? 1 : kKeyClassBits;
             g_last_classes = class_bits > 0;
             const T class_scale = static_cast<T>(t_exp.key_class_scale > 0 ? t_exp.key_class_scale : kKeyClassScalePercent) / T(100);
+            // (the tail class belongs to the one-bit key — "long rays first", what key_class_bits = 1 and the plan search's candidate both
+            //  select — and needs two more cell bits than the prefix: ray_key.h)
+            const bool tail = class_bits == 1 && cell_bits >= 2 && (t_exp.key_tail >= 0 ? t_exp.key_tail > 0 : kKeyTail > 0);
+            const T tail_frac = tail ? static_cast<T>(t_exp.key_tail_permille >= 0 ? t_exp.key_tail_permille : kKeyTailPermille) / T(1000) : T(-1);
             const uint32_t tiles = (n32 + kRadixTileU32 - 1) / kRadixTileU32;
             hipLaunchKernelGGL(ray_keys_kernel<T>, dim3(tiles), dim3(1024), 0, stream, d_rays, n32, lo[0], lo[1], lo[2], sc[0] * rescale, sc[1] * rescale,
                                sc[2] * rescale, keys, 1u << cell_bits, t_exp.key_curve == 0 ? 0 : cell_bits,      // Hilbert index by default (round 4); "key_curve" 0 = Morton
-                               class_bits, class_scale, hist, tiles);
+                               class_bits, class_scale, tail_frac, hist, tiles);
             first_hist_done = true;
             key_bits = 3 * cell_bits + 3;
         }
@@ -649,6 +694,18 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
         int rc = radix_sort_pairs<uint32_t>(keys, vals, kt, vt, n32, 1, key_bits, stream, hist, /*iota_vals=*/true, /*keys_wanted=*/false, &order, first_hist_done);
         if (rc) return release(rc);
         args.order = order;
+        // Ticket ranges: one per XCD, each the stretch of ONE key prefix (ticket_ranges_kernel reads the boundaries from the histogram
+        // the sort's last pass has left scanned in `hist`; the last digit holds the key's top key_bits - 8 (passes - 1) bits, so it must
+        // hold the three prefix bits whole). The kernel also zeroes the ticket counters: the timed pass has as many launches as before.
+        const int top_digit_bits = key_bits - 8 * ((key_bits + 7) / 8 - 1);
+        const bool align = args.parts == 8 && !args.one_shot && top_digit_bits >= 3 && (t_exp.range_align >= 0 ? t_exp.range_align > 0 : kRangeAlign > 0);
+        if (align) {
+            uint32_t* starts = hist + radix_sort_hist_words(n32, 1);
+            const uint32_t tiles = (n32 + kRadixTileU32 - 1) / kRadixTileU32;
+            hipLaunchKernelGGL(ticket_ranges_kernel, dim3(1), dim3(64), 0, stream, hist, tiles, 1u << (top_digit_bits - 3), n32, args.parts, args.part_size, starts, work);
+            if (const hipError_t e = hipGetLastError(); e != hipSuccess) return release(fail(BVH_AMD_ERR_HIP, std::string("intersect_rays: ticket_ranges_kernel: ") + hipGetErrorString(e)));
+            args.range_starts = starts;
+        } else if (const int rc0 = zero_tickets()) return release(rc0);
 #if defined(BVH_AMD_DEVELOPER)
         if (getenv("BVH_AMD_CHECK_ORDER")) {                  // developer check: is the order a set of valid ray indices when the sort has run?
             uint32_t* d_bad = nullptr;
