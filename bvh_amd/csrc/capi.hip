@@ -335,6 +335,7 @@ int on_resident_nodes(BvhImpl<T>* pb, Op op) {
 template <typename T> BvhImpl<T>* extract(BvhImpl<T>* pb, size_t root_id) {
     if (!pb) { set_error("extract: null bvh"); return nullptr; }
     BvhImpl<T>& b = *pb;
+    if (b.wait_refit()) return nullptr;                        // (a refit_* in flight on a non-blocking stream is not ordered before the copy-out below)
     if (make_nodes_resident<T>(b)) return nullptr;
     if (!b.d_prim_ids) { set_error("extract: the BVH has no device prim ids"); return nullptr; }
     auto out = std::make_unique<BvhImpl<T>>();
