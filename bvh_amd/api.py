@@ -614,10 +614,11 @@ def radius_search(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", max_p
     return _two_pass_lists("radius_search", call, n, q.device, max_per_query, counters, dt if distances else None)
 
 
-def _two_pass_lists(who: str, call, n: int, dev, max_per_query, counters: bool, dist_dtype=None):
+def _two_pass_lists(who: str, call, n: int, dev, max_per_query, counters: bool, dist_dtype=None, record_dtype=None):
     """Count pass, offsets, fill pass (or one pass into max_per_query slots) of call(counts, offsets, ids, dist, counters), the list
-    output of radius_search and the overlap queries: (offsets, ids, dist[, counts][, counters]); dist (None without dist_dtype) is
-    written beside ids."""
+    output of radius_search, the overlap queries and ray_hits: (offsets, ids, dist[, counts][, counters]); dist (None without
+    dist_dtype) is written beside ids. With record_dtype the list is ONE array of hit records, (total, 4) of that scalar type, in
+    the place of ids."""
     torch = _torch()
     cnt = torch.zeros(3, dtype=torch.int64, device=dev) if counters else None
     counts = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -631,13 +632,68 @@ def _two_pass_lists(who: str, call, n: int, dev, max_per_query, counters: bool, 
             raise ValueError("max_per_query must not be negative")
         offsets = torch.arange(n + 1, dtype=torch.int64, device=dev) * k
         total = n * k
-    ids = torch.empty(max(total, 1), dtype=torch.int32, device=dev)               # (never a null pointer: an empty result is still a list)
+    if record_dtype is not None:
+        ids = torch.empty((max(total, 1), 4), dtype=record_dtype, device=dev)
+    else:
+        ids = torch.empty(max(total, 1), dtype=torch.int32, device=dev)           # (never a null pointer: an empty result is still a list)
     dist = torch.empty(max(total, 1), dtype=dist_dtype, device=dev) if dist_dtype is not None else None
     _lib.check(call(counts.data_ptr() if max_per_query is not None else None, offsets.data_ptr(), ids.data_ptr(),
                     dist.data_ptr() if dist is not None else None, cnt.data_ptr() if counters else None), who)
     ids, dist = ids[:total], dist[:total] if dist is not None else None
     out = (offsets, ids, dist) if max_per_query is None else (offsets, ids, dist, counts)
     return out + (cnt,) if counters else out
+
+
+def _ray_query_args(bvh: Bvh, prims, rays, leaf: str, who: str):
+    """The checks of the all-hits ray queries: ((n, 8) rays, prims, scalar dtype)."""
+    torch = _torch()
+    if bvh.dim != 3:
+        raise TypeError(f"{who}: 3D trees only")
+    if leaf not in ("tri", "sphere"):
+        raise ValueError("leaf is 'tri' or 'sphere'")
+    dt = torch.float32 if bvh._s[1] == "f" else torch.float64
+    r = _dev(rays, 8)                                         # {org, dir, tmin, tmax}
+    p = _dev(prims)
+    if r.dtype != dt or p.dtype != dt:
+        raise TypeError("prims/rays dtype must match the BVH scalar type")
+    return r, p, dt
+
+
+def ray_hit_count(bvh: Bvh, prims, rays, leaf: str = "tri", robust: bool = False, sort_queries=None, counters: bool = False):
+    """For each ray, how many primitives the unshortened ray crosses (bvh3X_intersect_rays_all_* without lists): an int32 (n,)
+    tensor; with counters also (pairs, tests, leaves). prims and rays as for intersect."""
+    torch = _torch()
+    r, p, _ = _ray_query_args(bvh, prims, rays, leaf, "ray_hit_count")
+    n = r.shape[0]
+    counts = torch.zeros(n, dtype=torch.int32, device=r.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_rays_all_{leaf}")
+    flags = int(_sort_flags(sort_queries)) | (int(RayFlags.ROBUST) if robust else 0)
+    _lib.check(fn(bvh._h, p.data_ptr(), r.data_ptr(), n, flags, counts.data_ptr(), None, None, cnt.data_ptr() if counters else None, _stream()),
+               "ray_hit_count")
+    return (counts, cnt) if counters else counts
+
+
+def ray_hits(bvh: Bvh, prims, rays, leaf: str = "tri", robust: bool = False, max_per_ray=None, original_ids: bool = False, sort_queries=None,
+             counters: bool = False):
+    """For each ray, every primitive the unshortened ray {org, dir, tmin, tmax} crosses (bvh3X_intersect_rays_all_*): what the
+    reference's intersect reports to a leaf_fn that records a hit and never shortens the ray. The hits of a ray come in the order the
+    tree fixes (depth-first, left child first, ascending index inside a leaf), NOT sorted by t; equal t are all kept. prims are in BVH
+    order, as for intersect. Returns (offsets, hits): offsets int64 (n + 1,), ray r owns hits[offsets[r]:offsets[r + 1]], an (m, 4)
+    tensor of the records intersect writes (hits_to_numpy views it): {prim, t, u, v} for triangles, {prim, t0, t1, 0} for spheres;
+    prim is the BVH-order index, or bvh.prim_ids[i] with original_ids.
+      max_per_ray=None: exact lists - a count pass, the offsets on the device, one read of offsets[-1] to size the lists, a fill pass.
+      max_per_ray=k: one pass, k slots per ray (offsets = k * arange(n + 1)): the first k of each list, the unused slots holding
+        intersect's miss record {INVALID, the ray's tmax, 0, 0}; returns (offsets, hits, counts), counts (int32, untruncated) telling
+        which lists overflowed.
+    With counters, (pairs, tests, leaves) of the pass that wrote the lists is appended to the result."""
+    r, p, dt = _ray_query_args(bvh, prims, rays, leaf, "ray_hits")
+    n = r.shape[0]
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_rays_all_{leaf}")
+    flags = int(_sort_flags(sort_queries, original_ids)) | (int(RayFlags.ROBUST) if robust else 0)
+    call = lambda counts, offsets, hits, _, cnt: fn(bvh._h, p.data_ptr(), r.data_ptr(), n, flags, counts, offsets, hits, cnt, _stream())
+    out = _two_pass_lists("ray_hits", call, n, r.device, max_per_ray, counters, record_dtype=dt)
+    return out[:2] + out[3:]                                                        # (no distances beside the records)
 
 
 def _overlap_args(bvh: Bvh, bboxes, query_boxes, who: str):

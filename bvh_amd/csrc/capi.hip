@@ -558,6 +558,16 @@ int knn(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const
     return launch_knn<T>(*b, leaf, d_prims, d_queries4, n, k, flags, d_out_prims, d_out_dist, d_counts, d_counters, static_cast<hipStream_t>(stream));
 }
 
+template <typename T>
+int ray_hits(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const typename Family<T, 3>::Ray* d_rays, size_t n, unsigned flags,
+             uint32_t* d_counts, const uint64_t* d_offsets, typename HitOf<T>::Type* d_list_hits, bvh_amd_counters* d_counters, void* stream)
+{
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, n, "intersect_rays_all", &b)) return rc;
+    return launch_ray_hits<T>(*b, leaf, d_prims, reinterpret_cast<const T*>(d_rays), n, flags, d_counts, d_offsets, d_list_hits, d_counters,
+                              static_cast<hipStream_t>(stream));
+}
+
 // bvh3X_overlap_boxes / bvh3X_overlap_self: d_queries6 = NULL and n = the tree's primitive count in self mode.
 template <typename T>
 int overlap(const typename Family<T, 3>::Bvh* bvh, bool self, const T* d_bboxes, size_t n_boxes, const T* d_queries6, size_t n, unsigned flags,
@@ -798,6 +808,12 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_radius_search_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned flags, uint32_t* counts, \
                                       const uint64_t* offsets, uint32_t* list_prims, T* list_dist, bvh_amd_counters* cnt, void* s) { \
         return radius_search<T>(b, LEAF_SPHERE, prims, queries, n, flags, counts, offsets, list_prims, list_dist, cnt, s); } \
+    int bvh##S##_intersect_rays_all_tri(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, unsigned flags, uint32_t* counts, \
+                                        const uint64_t* offsets, bvh_hit##S* list_hits, bvh_amd_counters* cnt, void* s) {   \
+        return ray_hits<T>(b, LEAF_TRIANGLE, prims, rays, n, flags, counts, offsets, list_hits, cnt, s); }          \
+    int bvh##S##_intersect_rays_all_sphere(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, unsigned flags, uint32_t* counts, \
+                                           const uint64_t* offsets, bvh_hit##S* list_hits, bvh_amd_counters* cnt, void* s) { \
+        return ray_hits<T>(b, LEAF_SPHERE, prims, rays, n, flags, counts, offsets, list_hits, cnt, s); }            \
     int bvh##S##_knn_tri(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned k, unsigned flags, uint32_t* out_prims, \
                          T* out_dist, uint32_t* counts, bvh_amd_counters* cnt, void* s) {                           \
         return knn<T>(b, LEAF_TRIANGLE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }        \

@@ -278,6 +278,11 @@ int offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets,
 template <typename T>
 int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_boxes, const T* d_queries6, size_t n, unsigned flags, uint32_t* d_counts,
                    const uint64_t* d_offsets, uint32_t* d_list_prims, bvh_amd_counters* d_counters, hipStream_t stream);
+// ray_hits.hip: batched all-hits ray queries, n x {org, dir, tmin, tmax} -> per ray the count of primitives the unshortened ray crosses
+// and, with d_offsets, their hit records in the ray's segment [offsets[r], offsets[r + 1]) (flags: ROBUST, ORIGINAL_IDS, SORTED, UNSORTED)
+template <typename T>
+int launch_ray_hits(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T* d_rays, size_t n, unsigned flags, uint32_t* d_counts,
+                    const uint64_t* d_offsets, typename HitOf<T>::Type* d_list_hits, bvh_amd_counters* d_counters, hipStream_t stream);
 // instanced.hip: two-level scenes. A geometry = {tree, its BVH-order PrecomputedTri} (the layout of struct bvh_amd_geometry3f / 3d).
 // launch_instance_prepare: n_instances x object-to-world 3 x 4 -> world-to-object 3 x 4 (NaN: disabled), world boxes {min, max},
 // centres. launch_instanced: n_rays through `top` (built over those boxes, prim ids = instance indices) and the instances' geometries ->

@@ -1,7 +1,7 @@
-// What the per-lane bodies of the two list queries share (radius_body.inc, overlap_body.inc): the output arguments, and the one walk
+// What the per-lane bodies of the list queries share (radius_body.inc, overlap_body.inc, ray_hits_body.inc): the output arguments, and the one walk
 // that counts every match of a query and lists the first of them in the query's segment of a caller-sized buffer. The bodies supply
 // the query, the two tests and the stores. Kept as an include so that the host harnesses (tests/cpp/radius_body_host.cpp,
-// overlap_body_host.cpp) compile the very same text, through the bodies. Expects what point_walk.inc expects.
+// overlap_body_host.cpp, ray_hits_body_host.cpp) compile the very same text, through the bodies. Expects what point_walk.inc expects.
 #pragma once
 
 #include "point_walk.inc"
@@ -20,7 +20,7 @@ template <typename T>
 struct ListArgs : PointArgs<T> {
     uint32_t* counts;                          // optional: matches per query (never truncated), caller order
     const unsigned long long* offsets;         // Fill kernels only: query q owns [offsets[q], offsets[q + 1]) of the list arrays
-    uint32_t* list_prims;                      // Fill kernels only
+    uint32_t* list_prims;                      // Fill kernels only (unused by the ray query, whose list is one array of hit records)
 };
 
 // One query, one lane: depth-first walk from the root, the left child's subtree before the right's, a child entered iff

@@ -63,7 +63,7 @@ int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_b
         return fail(BVH_AMD_ERR_ARG, std::string(who) + ": " + std::to_string(n_boxes) + " boxes given, but prim_ids refers to primitive " +
                     std::to_string(largest) + " (the array is indexed by original primitive id)");
     const unsigned run_flags = self ? flags | BVH_AMD_RAY_UNSORTED : flags;
-    return point_query_run<T, true>(b, d_bboxes, d_queries6, n, run_flags, d_counters, sizeof(uint32_t), kBlock, kPointSortMin, kPointKeyBits, who, stream,
+    return point_query_run<T, kQueryBoxes>(b, d_bboxes, d_queries6, n, run_flags, d_counters, sizeof(uint32_t), kBlock, kPointSortMin, kPointKeyBits, who, stream,
                                     [&](const PointArgs<T>& args, T*) {
         const OverlapArgs<T> a{{args, d_counts, reinterpret_cast<const unsigned long long*>(d_offsets), d_list_prims}, b.d_prim_ids};
         // (the ladder's leaf kind is unused here: a box is a box)

@@ -1,6 +1,6 @@
-// The launch path of the batched point and box queries (closest.hip, radius.hip, knn.hip, overlap.hip), once: the thresholds, the
+// The launch path of the batched point, box and all-hits ray queries (closest.hip, radius.hip, knn.hip, overlap.hip, ray_hits.hip), once: the thresholds, the
 // argument checks they share, the driver (counters, depth pass, HBM spill, reading order, launches), the output check and the Fill
-// switch of the two list queries, and the kernels' counter epilogue. Expects common.h,
+// switch of the list queries, and the kernels' counter epilogue. Expects common.h,
 // trace_device.h, ray_key.h, query_order.h and the kind's body (point_walk.inc: PointArgs) to have been included.
 #pragma once
 
@@ -27,11 +27,13 @@ inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<u
 
 // The checks of a point query `who`, in their order: the flags, (an empty batch is accepted here: the caller returns when rc || n == 0,)
 // the tree's dimension, `required` (the pointers the kind cannot do without are there), `fault` (what the kind's own checks of its
-// pointers found, or null), the tree's device copy.
+// pointers found, or null), the tree's device copy. `more_flags`: bits this kind alone accepts (ray_hits.hip: BVH_AMD_RAY_ROBUST).
 template <typename T>
-int point_query_check(const BvhImpl<T>& b, size_t n, unsigned flags, bool required, const char* fault, const std::string& who) {
+int point_query_check(const BvhImpl<T>& b, size_t n, unsigned flags, bool required, const char* fault, const std::string& who, unsigned more_flags = 0u) {
     constexpr unsigned kAccepted = BVH_AMD_RAY_ORIGINAL_IDS | BVH_AMD_RAY_SORTED | BVH_AMD_RAY_UNSORTED;
-    if (flags & ~kAccepted) return fail(BVH_AMD_ERR_ARG, who + ": unsupported flags (ORIGINAL_IDS, SORTED and UNSORTED only)");
+    if (flags & ~(kAccepted | more_flags))
+        return fail(BVH_AMD_ERR_ARG, who + (more_flags & BVH_AMD_RAY_ROBUST ? ": unsupported flags (ROBUST, ORIGINAL_IDS, SORTED and UNSORTED only)"
+                                                                            : ": unsupported flags (ORIGINAL_IDS, SORTED and UNSORTED only)"));
     if (n == 0) return BVH_AMD_OK;
     if (b.dim != 3) return fail(BVH_AMD_ERR_ARG, who + ": 3D trees only");
     if (!required) return fail(BVH_AMD_ERR_ARG, who + ": null device pointer");
@@ -45,9 +47,10 @@ int point_query_check(const BvhImpl<T>& b, size_t n, unsigned flags, bool requir
 // per stack entry: a node word and whatever the kind keeps beside it; launches are cut to whole blocks of `lanes`), sorts the batch
 // when asked to or, left to itself, from sort_min queries on, and calls launch(args, deep_d2) for every slice: args holds what the
 // kinds share, deep_d2 the spill's other array (entry - 4 bytes per entry; null for a shallow tree). Owns the scratch behind both.
-// Boxes (overlap.hip): a query is a box of 6 scalars, ordered by the cell of its centre; d_queries may then be null when the batch is
-// not reordered (self mode: the lanes take their boxes from d_prims).
-template <typename T, bool Boxes = false, typename Launch>
+// kQueryBoxes (overlap.hip): a query is a box of 6 scalars, ordered by the cell of its centre; d_queries may then be null when the batch is
+// not reordered (self mode: the lanes take their boxes from d_prims). kQueryRays (ray_hits.hip): a query is a ray of 8 scalars, ordered
+// by the cell of its origin and the octant of its direction.
+template <typename T, int Kind = kQueryPoints, typename Launch>
 int point_query_run(const BvhImpl<T>& b, const T* d_prims, const T* d_queries, size_t n, unsigned flags, bvh_amd_counters* d_counters, size_t entry,
                     size_t lanes, size_t sort_min, int key_bits, const char* who, hipStream_t stream, Launch launch) {
     StreamScope scope(stream);
@@ -85,7 +88,7 @@ int point_query_run(const BvhImpl<T>& b, const T* d_prims, const T* d_queries, s
 
     const bool reorder = n < (size_t{1} << 31) && ((flags & BVH_AMD_RAY_SORTED) ? n > 1 : (flags & BVH_AMD_RAY_UNSORTED) ? false : n >= sort_min);
     if (reorder) {
-        const int rc = query_order<T, Boxes>(b, d_queries, n, key_bits, who, stream, &sort_mem, &sort_tag, &a.order);
+        const int rc = query_order<T, Kind>(b, d_queries, n, key_bits, who, stream, &sort_mem, &sort_tag, &a.order);
         if (rc) return release(rc);
     }
 
@@ -111,7 +114,7 @@ int point_query_dispatch(int leaf_kind, bool stats, bool deep, F f) {
     return stats ? leaf(std::true_type{}, std::false_type{}) : leaf(std::false_type{}, std::false_type{});
 }
 
-// The list queries (radius.hip, overlap.hip) have one more choice: f(leaf, stats, deep, fill), fill = the launch has offsets and
+// The list queries (radius.hip, overlap.hip, ray_hits.hip) have one more choice: f(leaf, stats, deep, fill), fill = the launch has offsets and
 // writes lists (the kernels <..., Fill = true>).
 template <typename F>
 int list_query_dispatch(int leaf_kind, bool stats, bool deep, bool fill, F f) {

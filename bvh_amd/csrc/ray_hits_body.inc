@@ -1,0 +1,100 @@
+// Per-lane body of the batched all-hits ray query (ray_hits.hip): every BVH-order primitive — a PrecomputedTri or a Sphere — that
+// the UNSHORTENED ray {org, dir, tmin, tmax} crosses, as a count and, optionally, a list of hit records in the ray's segment of a
+// caller-sized buffer. It is the third client of list_walk.inc, next to radius_body.inc and overlap_body.inc: the enter test is the
+// ray / box slab test of the ray walks (trace_device.h: ray_constants, slab_pair), the hit test their ray / primitive test
+// (tri_test.inc, the sphere expressions of trace_body.inc), both against the ray's own [tmin, tmax]: nothing a hit finds shortens
+// the ray, so the list is what the reference's intersect<false, Robust> reports to a leaf_fn that never shortens it.
+// Kept as an include so that tests/cpp/ray_hits_body_host.cpp compiles the very same text for the host (one emulated lane per ray).
+// Expects what point_walk.inc expects.
+#pragma once
+
+#include "list_walk.inc"
+
+namespace bvh_amd {
+
+namespace {
+
+constexpr int kRayHitsLds = kListLds;          // the kernel and the harness size their LDS array by this name
+
+template <typename T>
+struct RayHitsArgs : ListArgs<T> {             // queries = rays, 8 scalars each; counts = primitives crossed; list_prims is unused
+    typename HitOf<T>::Type* list_hits;        // Fill kernels only: the record intersect writes, one per listed primitive
+};
+
+// A list record is written once and not read again by the launch: one streaming store of 16 bytes (float) or two (double).
+__device__ inline void store_record(bvh_hit3f* out, uint32_t prim, float t, float u, float v) { store_hit_nt(out, prim, t, u, v); }
+__device__ inline void store_record(bvh_hit3d* out, uint32_t prim, double t, double u, double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    d2 a, b;
+    a.x = __longlong_as_double(static_cast<long long>(prim)); a.y = t; b.x = u; b.y = v;
+    __builtin_nontemporal_store(a, reinterpret_cast<d2*>(out));
+    __builtin_nontemporal_store(b, reinterpret_cast<d2*>(out) + 1);
+#else
+    store_hit(out, prim, t, u, v);
+#endif
+}
+
+// One ray, one lane: list_walk (which has the order of the walk and the shape of the output). A child is entered iff the ray's
+// [tmin, tmax] meets its box (bvh.h:177-180 through slab_pair; a NaN bound fails); a primitive matches iff the leaf test of the ray
+// walks accepts it against a copy of tmax that no other test has touched; the unused rest of a segment is padded with intersect's miss
+// record {BVH_AMD_INVALID, tmax, 0, 0}. A ray whose tmin or tmax is NaN is not walked (the `nan_ray` of slab_pair's callers); every
+// other ray is, whatever its direction or bounds. Slot `slot` of the launch (ray order[slot], or slot itself); `lane` indexes the HBM
+// spill (Deep), `tid` the LDS array. cnt += {pair records fetched, primitives tested, leaves visited}.
+template <typename T, int Leaf, bool Robust, bool Stats, bool Deep, bool Fill>
+__device__ inline void ray_hits_lane(const RayHitsArgs<T>& a, unsigned long long slot, uint32_t* lds_node, int tid, unsigned long long lane,
+                                     unsigned long long (&cnt)[3]) {
+    const unsigned long long qi = a.order ? a.order[slot] : slot;
+    T r[8];
+    load_ray(a.queries + 8ull * qi, r);
+    const T org[3] = { r[0], r[1], r[2] }, dir[3] = { r[3], r[4], r[5] };
+    const T tmin = r[6], ray_tmax = r[7];
+    T inv[3], aux[3];
+    uint32_t oct[3];
+    ray_constants<T, Robust, 3>(org, dir, inv, aux, oct);
+    const bool valid = tmin == tmin && ray_tmax == ray_tmax;
+
+    list_walk<T, Stats, Deep, Fill>(a, qi, valid, lds_node, tid, lane, cnt,
+        [&](const T (&box)[6]) {
+            // (slab_pair itself, the box in both places: the ray walks' arithmetic bit for bit, and the second copy folds away)
+            T l0, l1, r0, r1;
+            slab_pair<T, Robust, 3>(box, box, org, inv, aux, oct, tmin, ray_tmax, l0, l1, r0, r1);
+            return l0 <= l1;
+        },
+        [&](uint32_t i, unsigned long long at, bool room) {
+            if (Stats) ++cnt[1];
+            T tmax = ray_tmax;                                                  // this test's own copy: what it finds shortens nothing else
+            T hit_t = T(0), hit_u = T(0), hit_v = T(0);
+            bool accepted = false;
+            if (Leaf == LEAF_TRIANGLE) {                                        // tri.h:56-74
+                T p[12];
+                load_prim12(a.prims + 12ull * i, p);
+#define BVH_TRI_ACCEPTED accepted = true
+#include "tri_test.inc"
+#undef BVH_TRI_ACCEPTED
+            } else {                                                            // sphere.h:32-49, as trace_body.inc writes it
+                T s[4];
+                load_prim4(a.prims + 4ull * i, s);
+                const T o0 = org[0] - s[0], o1 = org[1] - s[1], o2 = org[2] - s[2];
+                const T qa = dot3(dir[0], dir[1], dir[2], dir[0], dir[1], dir[2]);
+                const T qb = T(2) * dot3(dir[0], dir[1], dir[2], o0, o1, o2);
+                const T qc = dot3(o0, o1, o2, o0, o1, o2) - s[3] * s[3];
+                const T delta = qb * qb - T(4) * qa * qc;
+                if (delta >= 0) {
+                    const T iv = -T(0.5) / qa;
+                    const T root = Num<T>::sqrt_(delta);
+                    const T t0 = pick_max((qb + root) * iv, tmin);
+                    const T t1 = pick_min((qb - root) * iv, tmax);
+                    if (t0 <= t1) { hit_t = t0; hit_u = t1; hit_v = T(0); accepted = true; }
+                }
+            }
+            if (!accepted) return false;
+            if (room) store_record(a.list_hits + at, a.prim_ids ? a.prim_ids[i] : i, hit_t, hit_u, hit_v);
+            return true;
+        },
+        [&](unsigned long long at) { store_record(a.list_hits + at, BVH_AMD_INVALID, ray_tmax, T(0), T(0)); });
+}
+
+} // namespace
+
+} // namespace bvh_amd

@@ -320,6 +320,8 @@ template <> struct Api<float, 3> {
     static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3f_closest_points_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
     static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
+    static int all_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3f_intersect_rays_all_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, counts, offsets, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
+    static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3f_intersect_rays_all_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, counts, offsets, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_boxes(h, static_cast<const float*>(bb), nb, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
@@ -363,6 +365,8 @@ template <> struct Api<double, 3> {
     static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3d_closest_points_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
     static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
+    static int all_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3d_intersect_rays_all_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, counts, offsets, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
+    static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3d_intersect_rays_all_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, counts, offsets, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_boxes(h, static_cast<const double*>(bb), nb, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
@@ -1053,6 +1057,76 @@ void overlap_self_batch(const Bvh<Node>& bvh, const DeviceArray<BBox<typename No
     static_assert(Node::dimension == 3, "overlap queries: 3D trees only");
     detail::overlap_host([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
         return Api<T, 3>::overlap_self(bvh.device(), bboxes.data(), bboxes.size(), flags, c, o, l); }, bvh.prim_ids.size(), offsets, list_prims, "overlap_self");
+}
+
+// For each ray, every primitive the UNSHORTENED ray crosses (include/bvh_amd.h: bvh3X_intersect_rays_all_*): what Bvh::intersect<false,
+// IsRobust> reports to a leaf_fn that records a hit and never shortens the ray, as the records intersect_batch writes ({prim, t, u, v};
+// {prim, t0, t1, 0} for spheres), in the order the tree fixes (depth-first, left child first, ascending index inside a leaf), NOT
+// sorted by t. Device form: any of the outputs may be null, as in the C ABI - `counts` (rays.size() entries: untruncated list
+// lengths), `offsets` (rays.size() + 1 entries; null = count pass) with `list_hits` (the unused rest of a segment holds intersect_batch's
+// miss record). `flags`: BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED. Host form: exact lists, ray r's hits are
+// list_hits[offsets[r] .. offsets[r + 1]).
+namespace detail {
+template <typename T>
+using AllHitsFn = int (*)(const typename Api<T, 3>::Handle*, const void*, const void*, size_t, unsigned, uint32_t*, const uint64_t*, void*);
+template <typename T>
+void all_hits_device(AllHitsFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, const DeviceArray<Ray<T, 3>>& rays, unsigned flags,
+                     DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<Hit<T>>* list_hits, const char* what) {
+    const size_t n = rays.size();
+    if ((counts && counts->size() < n) || (offsets && offsets->size() < n + 1)) throw Error(std::string(what) + ": counts need n entries, offsets n + 1");
+    check(fn(h, prims, rays.data(), n, flags, counts ? counts->data() : nullptr, offsets ? offsets->data() : nullptr, list_hits ? list_hits->data() : nullptr), what);
+}
+// count, offsets on the device, one read of offsets[n] to size the lists, fill
+template <typename T>
+void all_hits_host(AllHitsFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, std::span<const Ray<T, 3>> rays, unsigned flags,
+                   std::vector<uint64_t>& offsets, std::vector<Hit<T>>& list_hits, const char* what) {
+    const size_t n = rays.size();
+    offsets.assign(n + 1, 0);
+    list_hits.clear();
+    if (n == 0) return;
+    DeviceArray<Ray<T, 3>> d_rays(rays);
+    DeviceArray<uint32_t> d_counts(n);
+    DeviceArray<uint64_t> d_offsets(n + 1);
+    all_hits_device<T>(fn, h, prims, d_rays, flags, &d_counts, nullptr, nullptr, what);
+    check(bvh_amd_offsets_from_counts(d_counts.data(), n, d_offsets.data(), nullptr), "offsets_from_counts");
+    d_offsets.download(std::span<uint64_t>(offsets));
+    const size_t total = static_cast<size_t>(offsets[n]);
+    list_hits.resize(total);
+    if (total == 0) return;
+    DeviceArray<Hit<T>> d_list(total);
+    all_hits_device<T>(fn, h, prims, d_rays, flags, nullptr, &d_offsets, &d_list, what);
+    d_list.download(std::span<Hit<T>>(list_hits));
+}
+template <bool IsRobust> constexpr unsigned all_hits_flags(unsigned flags) { return flags | (IsRobust ? unsigned(BVH_AMD_RAY_ROBUST) : 0u); }
+} // namespace detail
+
+template <bool IsRobust, typename Node>
+void intersect_all_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, const DeviceArray<Ray<typename Node::Scalar, 3>>& rays,
+                         DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<Hit<typename Node::Scalar>>* list_hits, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "all-hits ray queries: 3D trees only");
+    detail::all_hits_device<T>(&Api<T, 3>::all_hits_tri, bvh.device(), prims.data(), rays, detail::all_hits_flags<IsRobust>(flags), counts, offsets, list_hits, "intersect_rays_all_tri");
+}
+template <bool IsRobust, typename Node>
+void intersect_all_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, const DeviceArray<Ray<typename Node::Scalar, 3>>& rays,
+                         DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<Hit<typename Node::Scalar>>* list_hits, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "all-hits ray queries: 3D trees only");
+    detail::all_hits_device<T>(&Api<T, 3>::all_hits_sphere, bvh.device(), spheres.data(), rays, detail::all_hits_flags<IsRobust>(flags), counts, offsets, list_hits, "intersect_rays_all_sphere");
+}
+template <bool IsRobust, typename Node>
+void intersect_all_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, std::span<const Ray<typename Node::Scalar, 3>> rays,
+                         std::vector<uint64_t>& offsets, std::vector<Hit<typename Node::Scalar>>& list_hits, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "all-hits ray queries: 3D trees only");
+    detail::all_hits_host<T>(&Api<T, 3>::all_hits_tri, bvh.device(), prims.data(), rays, detail::all_hits_flags<IsRobust>(flags), offsets, list_hits, "intersect_rays_all_tri");
+}
+template <bool IsRobust, typename Node>
+void intersect_all_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, std::span<const Ray<typename Node::Scalar, 3>> rays,
+                         std::vector<uint64_t>& offsets, std::vector<Hit<typename Node::Scalar>>& list_hits, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "all-hits ray queries: 3D trees only");
+    detail::all_hits_host<T>(&Api<T, 3>::all_hits_sphere, bvh.device(), spheres.data(), rays, detail::all_hits_flags<IsRobust>(flags), offsets, list_hits, "intersect_rays_all_sphere");
 }
 
 // Two-level scenes (include/bvh_amd.h: bvh3X_instance_prepare / bvh3X_intersect_rays_instanced): a table of geometries {tree, its

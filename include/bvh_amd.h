@@ -618,6 +618,49 @@ BVH_AMD_API int bvh3f_overlap_self(const struct bvh3f*, const float* d_bboxes, s
 BVH_AMD_API int bvh3d_overlap_self(const struct bvh3d*, const double* d_bboxes, size_t n_boxes, unsigned flags,
     uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
 
+/* ---- batched all-hits ray queries: for each ray, every primitive it crosses --------------------------------------------------------- */
+/* Rays and primitives as for bvh3X_intersect_rays_* (n x {org, dir, tmin, tmax}; BVH-order PrecomputedTri or Sphere<T, 3>).
+ *   result:  every BVH-order index i that (1) passes the leaf test of bvh3X_intersect_rays_* (tri.h:56-74 / sphere.h:32-49) against
+ *            the UNSHORTENED ray: tmax is never updated between tests, and (2) all of whose ancestors' boxes pass the node test
+ *            (bvh.h:177-180) against the unshortened [tmin, tmax]; a root that is a leaf is tested without a box test. That is the
+ *            set the reference's intersect<false, IsRobust> reports to a leaf_fn that records a hit and never shortens the ray.
+ *            Each hit is the record bvh3X_intersect_rays_* writes, with the same (t, u, v) bits: {prim, t, u, v} for a triangle,
+ *            {prim, t0, t1, 0} for a sphere. Whenever closest-hit bvh3X_intersect_rays_* with the same ROBUST flag hits, the ray's
+ *            list holds that record byte for byte (every test that passes with a shortened tmax passes with the original one);
+ *            whenever it misses, the count is 0. For a sphere "that record" is its prim and t0: t1 = min(exit, tmax), and
+ *            closest-hit clips it to the tmax it has shortened so far, while the list holds the unclipped one.
+ *   order:   that of bvhXX_radius_search_*: depth-first, a node's left child (first_id) before its right, ascending index inside a
+ *            leaf. NOT sorted by t and without near / far reordering; equal t are all kept. A caller who wants hits along the ray
+ *            sorts each segment by (t, prim).
+ *   output:  that of bvhXX_radius_search_*, with one array of hit records in place of its two list arrays: d_counts[r] (n entries,
+ *            or NULL) is NEVER truncated. d_offsets (n + 1 entries, or NULL = count pass, no record written): ray r owns
+ *            [d_offsets[r], d_offsets[r + 1]) of d_list_hits (required iff d_offsets); the first min(count, segment length) hits are
+ *            written there in walk order, the rest of the segment is padded with the miss record of bvh3X_intersect_rays_*,
+ *            {BVH_AMD_INVALID, the ray's tmax bits, 0, 0}; nothing outside a segment is written and a segment whose offsets do not
+ *            ascend is empty. At least one of d_counts and d_offsets must be given. Count pass, bvh_amd_offsets_from_counts, fill
+ *            pass = exact compressed-sparse-row lists; d_offsets = k * {0, 1, ..., n} = k slots per ray in one pass, d_counts
+ *            telling which lists overflowed.
+ *   invalid: a ray whose tmin or tmax is NaN has count 0 and a fully padded segment. Every other ray is walked, including one with
+ *            tmin > tmax, a zero direction or NaN components: it gets whatever the two tests produce, as in the reference.
+ *   flags:   BVH_AMD_RAY_ROBUST selects the robust node test (the default is the fast one), as for bvh3X_intersect_rays_*;
+ *            BVH_AMD_RAY_ORIGINAL_IDS stores prim_ids[i] in the records (the order stays the walk's); BVH_AMD_RAY_SORTED /
+ *            BVH_AMD_RAY_UNSORTED force / forbid reading the batch in the order of the rays' origin cells and direction octants (with
+ *            neither, batches of >= 1M rays are reordered). BVH_AMD_RAY_ANY_HIT and any other bit: BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * A ray's count and list depend only on the tree, the primitives, the ray and ROBUST / ORIGINAL_IDS: not on batch size, position or
+ * order, the reordering flags, the stream or the thread. d_counters (optional) receives {pair records fetched, primitives tested,
+ * leaves visited}. Alignment: d_prims and d_rays 16 bytes, d_offsets and d_counters 8, d_counts 4, d_list_hits to the size of its
+ * record (16 / 32). 3D trees only; a 2D tree, a NULL handle, a NULL or misaligned pointer, the forbidden output combinations and a
+ * tree without a device copy are refused with BVH_AMD_ERR_ARG. Re-entrant on a const tree (no work slot of the tree is claimed).
+ * Not offered: the 2D families, the k nearest hits by t, hits sorted by t, instanced (two-level) scenes. */
+BVH_AMD_API int bvh3f_intersect_rays_all_tri(const struct bvh3f*, const float* d_tris12, const struct bvh_ray3f* d_rays, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, struct bvh_hit3f* d_list_hits, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_intersect_rays_all_tri(const struct bvh3d*, const double* d_tris12, const struct bvh_ray3d* d_rays, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, struct bvh_hit3d* d_list_hits, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_intersect_rays_all_sphere(const struct bvh3f*, const float* d_sph4, const struct bvh_ray3f* d_rays, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, struct bvh_hit3f* d_list_hits, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_intersect_rays_all_sphere(const struct bvh3d*, const double* d_sph4, const struct bvh_ray3d* d_rays, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, struct bvh_hit3d* d_list_hits, struct bvh_amd_counters* d_counters, void* stream);
+
 /* ---- batched instanced ray queries: a two-level scene with transforms ---------------------------------------------------------- */
 /* A scene is a table of geometries {tree, its BVH-order PrecomputedTri, as bvh3X_intersect_rays_tri takes them}, n_instances
  * instances {object-to-world matrix, geometry index}, and a top tree: an ordinary bvh3X built over the instances' world boxes,
