@@ -154,6 +154,8 @@ _SIGS_T = {
     "bvh{S}_radius_search_sphere": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P, _P, _P, _P]),
     "bvh{S}_intersect_rays_all_tri": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_intersect_rays_all_sphere": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P, _P, _P]),
+    "bvh{S}_intersect_rays_nearest_tri": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P]),
+    "bvh{S}_intersect_rays_nearest_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P]),
     "bvh{S}_knn_tri": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_knn_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_overlap_boxes": (_I, [_P, _P, _Z, _P, _Z, _U, _P, _P, _P, _P, _P]),
@@ -201,6 +203,7 @@ _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_inter
             "bvh{S}_closest_points_tri", "bvh{S}_closest_points_sphere",                              # and the closest-point queries
             "bvh{S}_radius_search_tri", "bvh{S}_radius_search_sphere",                                # and the radius queries
             "bvh{S}_intersect_rays_all_tri", "bvh{S}_intersect_rays_all_sphere",                      # and the all-hits ray queries
+            "bvh{S}_intersect_rays_nearest_tri", "bvh{S}_intersect_rays_nearest_sphere",              # and the nearest-hits ray queries
             "bvh{S}_knn_tri", "bvh{S}_knn_sphere",                                                    # and the k-nearest queries
             "bvh{S}_overlap_boxes", "bvh{S}_overlap_self",                                            # and the box-overlap queries
             "bvh{S}_instance_prepare", "bvh{S}_intersect_rays_instanced",                             # and the instanced ray queries

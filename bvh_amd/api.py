@@ -696,6 +696,35 @@ def ray_hits(bvh: Bvh, prims, rays, leaf: str = "tri", robust: bool = False, max
     return out[:2] + out[3:]                                                        # (no distances beside the records)
 
 
+RAY_NEAREST_MAX_K = 64                          # BVH_AMD_RAY_NEAREST_MAX_K
+
+
+def ray_hits_nearest(bvh: Bvh, prims, rays, k: int, leaf: str = "tri", robust: bool = False, original_ids: bool = False, sort_queries=None,
+                     counters: bool = False):
+    """For each ray, the first k primitives it crosses, front to back (bvh3X_intersect_rays_nearest_*): the k smallest (t, BVH-order
+    index) among the primitives the walk tests and the unshortened ray {org, dir, tmin, tmax} crosses, ascending; equal t sort by
+    index. k = 1 is intersect's hit (the lowest index where primitives tie at its t); k >= a ray's ray_hits count gives that list
+    sorted by (t, prim), byte for byte. prims are in BVH order, as for intersect. Returns (hits, counts): hits (n, k, 4), the
+    records intersect writes (hits_to_numpy views them as n * k records): {prim, t, u, v} for triangles, {prim, t0, t1, 0} for spheres;
+    prim is the BVH-order index, or bvh.prim_ids[i] with original_ids; the unused slots of a row hold intersect's miss record
+    {INVALID, the ray's tmax, 0, 0}. counts int32 (n,): the valid records of each row. With counters, (pairs, tests, leaves) is
+    appended to the result. sort_queries: True / False force / forbid reordering the batch internally (None: the library decides)."""
+    torch = _torch()
+    k = int(k)
+    if not 1 <= k <= RAY_NEAREST_MAX_K:
+        raise ValueError(f"k must be in [1, {RAY_NEAREST_MAX_K}]")
+    r, p, dt = _ray_query_args(bvh, prims, rays, leaf, "ray_hits_nearest")
+    n = r.shape[0]
+    hits = torch.empty((n, k, 4), dtype=dt, device=r.device)
+    counts = torch.zeros(n, dtype=torch.int32, device=r.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_rays_nearest_{leaf}")
+    flags = int(_sort_flags(sort_queries, original_ids)) | (int(RayFlags.ROBUST) if robust else 0)
+    _lib.check(fn(bvh._h, p.data_ptr(), r.data_ptr(), n, k, flags, hits.data_ptr(), counts.data_ptr(), cnt.data_ptr() if counters else None, _stream()),
+               "ray_hits_nearest")
+    return (hits, counts, cnt) if counters else (hits, counts)
+
+
 def _overlap_args(bvh: Bvh, bboxes, query_boxes, who: str):
     """The checks of the box-overlap queries: ((n_boxes, 6) boxes by original id, (n, 6) query boxes or None)."""
     if bvh.dim != 3:

@@ -12,7 +12,7 @@
 //   * the candidates: a binary max-heap of k {d2, index} per lane in LDS, [slot][lane] arrays (a lane's bank does not depend on the
 //     slot), the worst pair and the fill count in registers; heapsorted in place at the end and written as one row;
 //   * k is a run-time argument: the LDS is dynamic, (k + kKnnLds) * (sizeof(T) + 4) bytes per lane, and a block has 256, 128 or 64
-//     lanes, whichever keeps the most queries resident on a CU for that k (knn_block_lanes);
+//     lanes, whichever keeps the most queries resident on a CU for that k (knn_lanes.h: knn_block_lanes);
 //   * the stack: kKnnLds entries in LDS, the rest of 64 in per-lane scratch, beyond 64 (deep trees) in HBM (point_walk.inc);
 //   * optionally the batch is read in the order of the Hilbert cell of each point in the root box (query_order.h). Rows are always
 //     written in the caller's order.
@@ -25,6 +25,7 @@
 #include "query_order.h"
 #include "knn_body.inc"
 #include "point_query.h"
+#include "knn_lanes.h"
 
 namespace bvh_amd {
 
@@ -40,27 +41,6 @@ __global__ void __launch_bounds__(kBlock) knn_kernel(KnnArgs<T> a) {
     unsigned long long cnt[3] = {0, 0, 0};
     if (lane < a.n) knn_lane<T, Leaf, Stats, Deep>(a, a.first + lane, lds, stride, tid, lane, cnt);
     if (Stats) add_counters(a.counters, cnt, tid);
-}
-
-// Lanes per block: of 256 / 128 / 64, the size that keeps the most lanes resident on a CU — whole blocks of (k + kKnnLds) *
-// (sizeof(T) + 4) bytes per lane in the 160 KB of LDS, a block within 64 KB, at most 8 waves per SIMD — ties to the larger block. The
-// LDS a lane needs is fixed by k; the block size only decides how much of the CU's LDS the rounding to whole blocks wastes, so the
-// choice is not monotonic in k: floats take 256 lanes at k = 1, 8, 17, 128 at k = 9, 32 and 64 at k = 16, 33 .. 64; doubles 256 at
-// k = 5, 9, 128 at k = 7, 16, 17 and 64 at k = 1, 8, 32 .. 64 ("k-nearest queries", has the table).
-constexpr size_t kKnnBlockLds = size_t{64} << 10;
-constexpr size_t kKnnCuLds = size_t{160} << 10;
-constexpr size_t kKnnCuLanes = 8 * 4 * kWave;
-template <typename T>
-unsigned knn_block_lanes(unsigned k) {
-    unsigned best = kWave;
-    size_t best_resident = 0;
-    for (unsigned lanes = kBlock; lanes >= unsigned(kWave); lanes /= 2) {
-        const size_t bytes = knn_lds_bytes<T>(k, lanes);
-        if (bytes > kKnnBlockLds) continue;
-        const size_t resident = std::min(kKnnCuLds / bytes * lanes, kKnnCuLanes);
-        if (resident > best_resident) { best = lanes; best_resident = resident; }
-    }
-    return best;
 }
 
 } // namespace

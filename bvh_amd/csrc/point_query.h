@@ -1,4 +1,4 @@
-// The launch path of the batched point, box and all-hits ray queries (closest.hip, radius.hip, knn.hip, overlap.hip, ray_hits.hip), once: the thresholds, the
+// The launch path of the batched point, box and ray list / row queries (closest.hip, radius.hip, knn.hip, overlap.hip, ray_hits.hip, ray_nearest.hip), once: the thresholds, the
 // argument checks they share, the driver (counters, depth pass, HBM spill, reading order, launches), the output check and the Fill
 // switch of the list queries, and the kernels' counter epilogue. Expects common.h,
 // trace_device.h, ray_key.h, query_order.h and the kind's body (point_walk.inc: PointArgs) to have been included.

@@ -63,6 +63,7 @@ __device__ inline void ray_hits_lane(const RayHitsArgs<T>& a, unsigned long long
         },
         [&](uint32_t i, unsigned long long at, bool room) {
             if (Stats) ++cnt[1];
+            // (TWIN COPY of the two tests below: ray_nearest_test in ray_nearest_body.inc; a fix to one belongs in the other)
             T tmax = ray_tmax;                                                  // this test's own copy: what it finds shortens nothing else
             T hit_t = T(0), hit_u = T(0), hit_v = T(0);
             bool accepted = false;

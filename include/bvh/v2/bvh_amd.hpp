@@ -322,6 +322,8 @@ template <> struct Api<float, 3> {
     static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
     static int all_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3f_intersect_rays_all_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, counts, offsets, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3f_intersect_rays_all_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, counts, offsets, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
+    static int nearest_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3f_intersect_rays_nearest_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, k, f, static_cast<bvh_hit3f*>(hits), counts, nullptr, nullptr); }
+    static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3f_intersect_rays_nearest_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, k, f, static_cast<bvh_hit3f*>(hits), counts, nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_boxes(h, static_cast<const float*>(bb), nb, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
@@ -367,6 +369,8 @@ template <> struct Api<double, 3> {
     static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
     static int all_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3d_intersect_rays_all_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, counts, offsets, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3d_intersect_rays_all_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, counts, offsets, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
+    static int nearest_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3d_intersect_rays_nearest_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, k, f, static_cast<bvh_hit3d*>(hits), counts, nullptr, nullptr); }
+    static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3d_intersect_rays_nearest_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, k, f, static_cast<bvh_hit3d*>(hits), counts, nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_boxes(h, static_cast<const double*>(bb), nb, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
@@ -1127,6 +1131,68 @@ void intersect_all_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename
     using T = typename Node::Scalar;
     static_assert(Node::dimension == 3, "all-hits ray queries: 3D trees only");
     detail::all_hits_host<T>(&Api<T, 3>::all_hits_sphere, bvh.device(), spheres.data(), rays, detail::all_hits_flags<IsRobust>(flags), offsets, list_hits, "intersect_rays_all_sphere");
+}
+
+// For each ray, the first k primitives it crosses, front to back (include/bvh_amd.h: bvh3X_intersect_rays_nearest_*), k in
+// [1, BVH_AMD_RAY_NEAREST_MAX_K]: row r is hits[k * r .. k * r + k), the k smallest (t, BVH-order index) among the primitives the walk
+// tests, ascending, as the records intersect_batch writes ({prim, t, u, v}; {prim, t0, t1, 0} for spheres); the unused slots hold
+// intersect_batch's miss record, and counts[r] says how many are used. k = 1 is intersect_batch's hit (the lowest index where
+// primitives tie at its t); k >= a ray's intersect_all_batch count gives that list sorted by (t, prim). Device form: `counts` may be
+// null. `flags`: BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED.
+namespace detail {
+template <typename T>
+using NearestHitsFn = int (*)(const typename Api<T, 3>::Handle*, const void*, const void*, size_t, unsigned, unsigned, void*, uint32_t*);
+template <typename T>
+void nearest_hits_device(NearestHitsFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, const DeviceArray<Ray<T, 3>>& rays, unsigned k, unsigned flags,
+                         DeviceArray<Hit<T>>& hits, DeviceArray<uint32_t>* counts, const char* what) {
+    const size_t n = rays.size();
+    if (hits.size() < n * k || (counts && counts->size() < n)) throw Error(std::string(what) + ": hits need n * k records, counts n entries");
+    check(fn(h, prims, rays.data(), n, k, flags, hits.data(), counts ? counts->data() : nullptr), what);
+}
+template <typename T>
+void nearest_hits_host(NearestHitsFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, std::span<const Ray<T, 3>> rays, unsigned k, unsigned flags,
+                       std::vector<Hit<T>>& hits, std::vector<uint32_t>* counts, const char* what) {
+    const size_t n = rays.size();
+    if (k == 0 || k > BVH_AMD_RAY_NEAREST_MAX_K) throw Error(std::string(what) + ": k must be in [1, " + std::to_string(BVH_AMD_RAY_NEAREST_MAX_K) + "]");
+    hits.resize(n * k);
+    if (counts) counts->assign(n, 0);
+    if (n == 0) return;
+    DeviceArray<Ray<T, 3>> d_rays(rays);
+    DeviceArray<Hit<T>> d_hits(n * k);
+    DeviceArray<uint32_t> d_counts(n);
+    nearest_hits_device<T>(fn, h, prims, d_rays, k, flags, d_hits, &d_counts, what);
+    d_hits.download(std::span<Hit<T>>(hits));
+    if (counts) d_counts.download(std::span<uint32_t>(*counts));
+}
+} // namespace detail
+
+template <bool IsRobust, typename Node>
+void intersect_nearest_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, const DeviceArray<Ray<typename Node::Scalar, 3>>& rays,
+                             unsigned k, DeviceArray<Hit<typename Node::Scalar>>& hits, DeviceArray<uint32_t>* counts, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "nearest-hits ray queries: 3D trees only");
+    detail::nearest_hits_device<T>(&Api<T, 3>::nearest_hits_tri, bvh.device(), prims.data(), rays, k, detail::all_hits_flags<IsRobust>(flags), hits, counts, "intersect_rays_nearest_tri");
+}
+template <bool IsRobust, typename Node>
+void intersect_nearest_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, const DeviceArray<Ray<typename Node::Scalar, 3>>& rays,
+                             unsigned k, DeviceArray<Hit<typename Node::Scalar>>& hits, DeviceArray<uint32_t>* counts, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "nearest-hits ray queries: 3D trees only");
+    detail::nearest_hits_device<T>(&Api<T, 3>::nearest_hits_sphere, bvh.device(), spheres.data(), rays, k, detail::all_hits_flags<IsRobust>(flags), hits, counts, "intersect_rays_nearest_sphere");
+}
+template <bool IsRobust, typename Node>
+void intersect_nearest_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, std::span<const Ray<typename Node::Scalar, 3>> rays,
+                             unsigned k, std::vector<Hit<typename Node::Scalar>>& hits, std::vector<uint32_t>* counts, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "nearest-hits ray queries: 3D trees only");
+    detail::nearest_hits_host<T>(&Api<T, 3>::nearest_hits_tri, bvh.device(), prims.data(), rays, k, detail::all_hits_flags<IsRobust>(flags), hits, counts, "intersect_rays_nearest_tri");
+}
+template <bool IsRobust, typename Node>
+void intersect_nearest_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, std::span<const Ray<typename Node::Scalar, 3>> rays,
+                             unsigned k, std::vector<Hit<typename Node::Scalar>>& hits, std::vector<uint32_t>* counts, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "nearest-hits ray queries: 3D trees only");
+    detail::nearest_hits_host<T>(&Api<T, 3>::nearest_hits_sphere, bvh.device(), spheres.data(), rays, k, detail::all_hits_flags<IsRobust>(flags), hits, counts, "intersect_rays_nearest_sphere");
 }
 
 // Two-level scenes (include/bvh_amd.h: bvh3X_instance_prepare / bvh3X_intersect_rays_instanced): a table of geometries {tree, its

@@ -651,7 +651,8 @@ BVH_AMD_API int bvh3d_overlap_self(const struct bvh3d*, const double* d_bboxes, 
  * leaves visited}. Alignment: d_prims and d_rays 16 bytes, d_offsets and d_counters 8, d_counts 4, d_list_hits to the size of its
  * record (16 / 32). 3D trees only; a 2D tree, a NULL handle, a NULL or misaligned pointer, the forbidden output combinations and a
  * tree without a device copy are refused with BVH_AMD_ERR_ARG. Re-entrant on a const tree (no work slot of the tree is claimed).
- * Not offered: the 2D families, the k nearest hits by t, hits sorted by t, instanced (two-level) scenes. */
+ * Not offered: the 2D families, hits sorted by t (the first k of them are bvh3X_intersect_rays_nearest_*, below), instanced
+ * (two-level) scenes. */
 BVH_AMD_API int bvh3f_intersect_rays_all_tri(const struct bvh3f*, const float* d_tris12, const struct bvh_ray3f* d_rays, size_t n, unsigned flags,
     uint32_t* d_counts, const uint64_t* d_offsets, struct bvh_hit3f* d_list_hits, struct bvh_amd_counters* d_counters, void* stream);
 BVH_AMD_API int bvh3d_intersect_rays_all_tri(const struct bvh3d*, const double* d_tris12, const struct bvh_ray3d* d_rays, size_t n, unsigned flags,
@@ -660,6 +661,46 @@ BVH_AMD_API int bvh3f_intersect_rays_all_sphere(const struct bvh3f*, const float
     uint32_t* d_counts, const uint64_t* d_offsets, struct bvh_hit3f* d_list_hits, struct bvh_amd_counters* d_counters, void* stream);
 BVH_AMD_API int bvh3d_intersect_rays_all_sphere(const struct bvh3d*, const double* d_sph4, const struct bvh_ray3d* d_rays, size_t n, unsigned flags,
     uint32_t* d_counts, const uint64_t* d_offsets, struct bvh_hit3d* d_list_hits, struct bvh_amd_counters* d_counters, void* stream);
+
+/* ---- batched nearest-hits ray queries: for each ray, the first k primitives it crosses, front to back ------------------------------- */
+/* Rays, primitives and records as for bvh3X_intersect_rays_all_*. k is in [1, BVH_AMD_RAY_NEAREST_MAX_K]; longer rows are the
+ * all-hits query's.
+ *   candidate: a BVH-order index i that the walk tests and that passes the leaf test of bvh3X_intersect_rays_* against the UNSHORTENED
+ *            ray. Its record is exactly the all-hits record: {prim, t, u, v} for a triangle, {prim, t0, t1 = min(exit, the ray's own
+ *            tmax), 0} for a sphere; the tmax the walk has shortened never enters a record.
+ *   row:     d_out_hits[r * k .. r * k + k) holds the k smallest (t, i) in lexicographic order among the candidates, ascending; equal
+ *            t sort by ascending BVH-order index (also under BVH_AMD_RAY_ORIGINAL_IDS, which maps the reported prim only). Unused
+ *            slots hold the miss record of bvh3X_intersect_rays_*, {BVH_AMD_INVALID, the ray's tmax bits, 0, 0}. d_counts[r] (n
+ *            entries, or NULL) = the valid records of row r, <= k. Nothing outside [0, n * k) records is written.
+ *   walk:    that of bvh3X_intersect_rays_*: depth-first, of two children the ray meets the one it enters first (l0 > r0 takes the
+ *            right one), the other stacked with its entry t. Both node tests (bvh.h:177-180) run against [tmin, worst]: worst is the
+ *            ray's tmax while fewer than k candidates are held, afterwards the t of the largest (t, i) held. A stacked entry is
+ *            dropped iff its entry t > worst. A leaf tests ascending i; while fewer than k are held every candidate is accepted,
+ *            afterwards a candidate is accepted iff (t, i) < (worst, worst's index), and it replaces the worst.
+ *   relation: k = 1: hit or miss and the t bits are those of closest-hit bvh3X_intersect_rays_* with the same ROBUST flag, and so is
+ *            prim unless two tested primitives tie at that t (closest-hit keeps the last one tested there, this query the lowest
+ *            index). k >= the ray's all-hits count: the row is the ray's bvh3X_intersect_rays_all_* list sorted by (t, prim), byte for
+ *            byte (nothing is pruned while fewer than k are held). In between, "smallest" is among the primitives the walk tests,
+ *            as for bvhXX_knn_*: the sorted all-hits prefix unless a box is computed to start behind a primitive it contains.
+ *   invalid: a ray whose tmin or tmax is NaN has count 0 and a fully padded row. Every other ray is walked, as for the all-hits query.
+ *   flags:   BVH_AMD_RAY_ROBUST, BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED as for the all-hits query (the
+ *            same reordering key; with neither, batches of >= 1M rays are reordered). BVH_AMD_RAY_ANY_HIT and any other bit:
+ *            BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * A ray's row and count depend only on the tree, the primitives, the ray, k and ROBUST / ORIGINAL_IDS: not on batch size, position or
+ * order, the reordering flags, the stream or the thread. d_counters (optional) receives {pair records fetched, primitives tested
+ * (the write-out's repeated tests not counted), leaves visited}. Alignment: d_prims and d_rays 16 bytes, d_out_hits to the size of
+ * its record (16 / 32), d_counters 8, d_counts 4. 3D trees only; k == 0 or k > BVH_AMD_RAY_NEAREST_MAX_K, a 2D tree, a NULL handle, a
+ * NULL d_prims, d_rays or d_out_hits, a misaligned pointer and a tree without a device copy are refused with BVH_AMD_ERR_ARG.
+ * Re-entrant on a const tree (no work slot of the tree is claimed). Not offered: the 2D families, instanced (two-level) scenes. */
+#define BVH_AMD_RAY_NEAREST_MAX_K 64
+BVH_AMD_API int bvh3f_intersect_rays_nearest_tri(const struct bvh3f*, const float* d_tris12, const struct bvh_ray3f* d_rays, size_t n, unsigned k,
+    unsigned flags, struct bvh_hit3f* d_out_hits, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_intersect_rays_nearest_tri(const struct bvh3d*, const double* d_tris12, const struct bvh_ray3d* d_rays, size_t n, unsigned k,
+    unsigned flags, struct bvh_hit3d* d_out_hits, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_intersect_rays_nearest_sphere(const struct bvh3f*, const float* d_sph4, const struct bvh_ray3f* d_rays, size_t n, unsigned k,
+    unsigned flags, struct bvh_hit3f* d_out_hits, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_intersect_rays_nearest_sphere(const struct bvh3d*, const double* d_sph4, const struct bvh_ray3d* d_rays, size_t n, unsigned k,
+    unsigned flags, struct bvh_hit3d* d_out_hits, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
 
 /* ---- batched instanced ray queries: a two-level scene with transforms ---------------------------------------------------------- */
 /* A scene is a table of geometries {tree, its BVH-order PrecomputedTri, as bvh3X_intersect_rays_tri takes them}, n_instances
