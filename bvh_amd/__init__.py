@@ -20,5 +20,5 @@ Everything computes in hand-written HIP kernels through the C-ABI of libbvh_amd.
 """
 from .api import (BinnedSahBuilder, MiniTreeBuilder, SplitHeuristic, Bvh, Config, DefaultBuilder, Quality, RayFlags, SweepSahBuilder, ThreadPool, prepare_trace,  # noqa: F401
                   HITD, HITF, INVALID, NODED, NODEF, NODE2D, NODE2F, closest_points, hits_to_numpy, intersect, precompute_tris, sphere_bounds,
-                  tri_bounds, gather, radius_count, radius_search, offsets_from_counts, ray_hit_count, ray_hits, ray_hits_nearest, RAY_NEAREST_MAX_K, knn, KNN_MAX_K, overlap_count, overlap_search, self_overlaps, instance_prepare, intersect_instanced, std_sort_ids, radix_sort_pairs, reinsertion_stats, last_optimize_profile, pinhole_rays, shade_eyelight)
+                  tri_bounds, gather, radius_count, radius_search, offsets_from_counts, ray_hit_count, ray_hits, ray_hits_nearest, RAY_NEAREST_MAX_K, knn, KNN_MAX_K, overlap_count, overlap_search, self_overlaps, instance_prepare, intersect_instanced, std_sort_ids, radix_sort_pairs, radix_order, reinsertion_stats, last_optimize_profile, pinhole_rays, shade_eyelight)
 from ._lib import BvhAmdError  # noqa: F401

@@ -99,6 +99,7 @@ _SIGS = {
     "bvh_amd_std_sort_ids3f": (_I, [_P, _Z, _P, _P]),
     "bvh_amd_std_sort_ids3d": (_I, [_P, _Z, _P, _P]),
     "bvh_amd_radix_sort_pairs_u32": (_I, [_P, _P, _Z, _I, _P]),
+    "bvh_amd_radix_order_u32": (_I, [_P, _Z, _I, _P, _P]),
     "bvh_amd_offsets_from_counts": (_I, [_P, _Z, _P, _P]),
 }
 _SIGS_T = {

@@ -935,3 +935,12 @@ def radix_sort_pairs(keys_u32, vals_u32, bits=32):
     v = _dev(vals_u32).to(torch.int32).clone()
     _lib.check(_lib.load().bvh_amd_radix_sort_pairs_u32(k.data_ptr(), v.data_ptr(), k.shape[0], bits, _stream()), "radix_sort_pairs")
     return k, v
+
+
+def radix_order(keys_u32, bits=32):
+    """The stable order of the keys by their low `bits` bits, as a reordered ray / query batch computes it (int32 tensor)."""
+    torch = _torch()
+    k = _dev(keys_u32).to(torch.int32).contiguous()
+    out = torch.empty(k.shape[0], dtype=torch.int32, device=k.device)
+    _lib.check(_lib.load().bvh_amd_radix_order_u32(k.data_ptr(), k.shape[0], bits, out.data_ptr(), _stream()), "radix_order")
+    return out

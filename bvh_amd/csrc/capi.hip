@@ -892,6 +892,11 @@ int bvh_amd_radix_sort_pairs_u32(uint32_t* d_keys, uint32_t* d_vals, size_t n, i
                            : fail(BVH_AMD_ERR_HIP, hipGetErrorString(e));
 }
 
+int bvh_amd_radix_order_u32(const uint32_t* d_keys, size_t n, int bits, uint32_t* d_order_out, void* stream) {
+    if (n >= (size_t{1} << 31)) return fail(BVH_AMD_ERR_ARG, "bvh_amd_radix_order_u32: fewer than 2^31 keys");
+    return radix_order_of_keys(d_keys, static_cast<uint32_t>(n), bits, d_order_out, static_cast<hipStream_t>(stream));
+}
+
 int bvh_amd_pinhole_rays3f(const float eye[3], const float dir[3], const float up[3], size_t w, size_t h, bvh_ray3f* d_rays, void* stream) {
     return launch_pinhole_rays<float>(eye, dir, up, w, h, reinterpret_cast<float*>(d_rays), static_cast<hipStream_t>(stream));
 }

@@ -347,6 +347,17 @@ constexpr int kRadixTileU32 = 8192;
 //  the values are sorted on return, `keys` is left in an unspecified state; vals_result != nullptr: exactly ceil(bits / 8) passes,
 //  *vals_result = whichever of vals / vals_tmp holds the sorted values, keys unspecified)
 size_t radix_sort_hist_words(uint32_t n, uint32_t batch);
+// The ORDER of one array of n < 2^31 32-bit keys by their low `bits` bits: the permutation the stable sort above gives iota values,
+// without the keys (what a reordered ray / query batch needs). One block of scratch, in 32-bit words from its start:
+//   [0, n) the keys (the caller's key kernel writes them; destroyed) | carry: the narrowed keys between passes | vals0, vals1: the
+//   two index arrays | hist: 256 x tiles counts, digit-major / tile-minor in tiles of kRadixTileU32 keys, + 256 digit totals.
+// first_hist_done: the key kernel has left the per-tile histogram of the keys' lowest byte in `hist`. *order = where the last pass
+// wrote (vals0 or vals1). Afterwards hist[d * tiles + t] is the offset of tile t WITHIN digit d of the LAST pass and
+// hist[256 * tiles + d] that digit's total. Entirely in stream order.
+struct RadixOrderLayout { size_t carry, vals0, vals1, hist, words; };
+RadixOrderLayout radix_order_layout(uint32_t n, int bits);
+int radix_sort_order(uint32_t* scratch, uint32_t n, int bits, hipStream_t stream, bool first_hist_done, uint32_t** order);
+int radix_order_of_keys(const uint32_t* d_keys, uint32_t n, int bits, uint32_t* d_order, hipStream_t stream);   // test entry: own scratch, own key kernel
 template <typename T>
 int std_sort_ids(uint32_t* d_ids, const T* d_keys, uint32_t n, uint32_t batch, uint32_t astride, uint32_t istride, hipStream_t stream);
 

@@ -99,10 +99,11 @@ template <typename T, int Kind = kQueryPoints>
 int query_order(const BvhImpl<T>& b, const T* d_queries, size_t n, int cell_bits, const char* who, hipStream_t stream, void** sort_mem,
                 ScratchTag* sort_tag, const uint32_t** order_out) {
     const uint32_t n32 = static_cast<uint32_t>(n);
-    const size_t words = 4 * n + radix_sort_hist_words(n32, 1);               // keys + tmp, indices + tmp, histogram
-    const hipError_t e = scratch_alloc(sort_mem, words * sizeof(uint32_t), sort_tag);
+    const int key_bits = 3 * cell_bits + 3;
+    const RadixOrderLayout layout = radix_order_layout(n32, key_bits);        // keys, carried keys, indices + tmp, histogram + digit totals
+    const hipError_t e = scratch_alloc(sort_mem, layout.words * sizeof(uint32_t), sort_tag);
     if (e != hipSuccess) { *sort_mem = nullptr; return fail(BVH_AMD_ERR_HIP, std::string(who) + ": no scratch for the query sort: " + hipGetErrorString(e)); }
-    uint32_t *keys = static_cast<uint32_t*>(*sort_mem), *vals = keys + n, *kt = vals + n, *vt = kt + n, *hist = vt + n;
+    uint32_t *keys = static_cast<uint32_t*>(*sort_mem), *hist = keys + layout.hist;
     const uint32_t cells = 1u << cell_bits;
     T lo[3], sc[3];
     if (const int rc0 = b.wait_refit()) return rc0;                   // root_bounds follows a refit_* that changed the boxes on the device
@@ -123,8 +124,7 @@ int query_order(const BvhImpl<T>& b, const T* d_queries, size_t n, int cell_bits
                            keys, hist, tiles);
     BVH_HIP_TRY(hipGetLastError(), BVH_AMD_ERR_HIP);
     uint32_t* order = nullptr;
-    const int rc = radix_sort_pairs<uint32_t>(keys, vals, kt, vt, n32, 1, 3 * cell_bits + 3, stream, hist, /*iota_vals=*/true, /*keys_wanted=*/false, &order,
-                                              /*first_hist_done=*/true);
+    const int rc = radix_sort_order(keys, n32, key_bits, stream, /*first_hist_done=*/true, &order);
     if (rc) return rc;
     *order_out = order;
     return BVH_AMD_OK;

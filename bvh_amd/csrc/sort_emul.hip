@@ -817,6 +817,286 @@ int radix_sort_pairs(K* keys, uint32_t* vals, K* keys_tmp, uint32_t* vals_tmp, u
     return BVH_AMD_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// the ORDER of one array of 32-bit keys (the reordering of a ray / query batch)
+// ---------------------------------------------------------------------------------------------------
+// The same stable LSD sort for the callers that want only the permutation: one array, values = input positions, keys dropped. Two
+// things the general sort above pays for nothing then are left out.
+//  * After pass p only the key bits above 8 (p + 1) can still matter, so a pass carries `key >> 8` on in the narrowest of
+//    u32 / u16 / u8 that holds what is left, and the next pass (and its histogram) reads that type and always sorts by the lowest
+//    byte: 24-bit keys go u32 -> u16 -> u8 -> nothing, 25..32 bits u32 -> u32 -> u16 -> u8 -> nothing, 9..16 bits u32 -> u8 -> nothing.
+//  * The histogram (digit-major, tile-minor) is scanned by ONE launch of 256 blocks: block d turns digit d's tile counts into
+//    offsets within the digit and leaves the digit's total behind the table; every scatter block scans those 256 totals in LDS
+//    beside the scan of its own tile's digits. No block waits for another.
+// The tile is kRadixTileU32 keys whatever the key type: the callers' key kernels and ticket_ranges_kernel count in those tiles.
+namespace {
+
+constexpr int kOrderTile = kRadixTileU32, kOrderThreads = kOrderTile / 16, kOrderWaves = kOrderThreads / 64;
+
+// the test entry's key kernel: a copy of the keys and the first histogram, as ray_keys_kernel leaves them
+__global__ void __launch_bounds__(1024) k_order_copy_keys(const uint32_t* in, uint32_t n, uint32_t* keys, uint32_t* hist, uint32_t tiles) {
+    __shared__ uint32_t h[256];
+    if (threadIdx.x < 256) h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t base = blockIdx.x * uint32_t(kOrderTile);
+    for (int s0 = 0; s0 < kOrderTile / 1024; ++s0) {
+        const uint32_t i = base + uint32_t(s0) * 1024u + threadIdx.x;
+        if (i < n) {
+            const uint32_t key = in[i];
+            keys[i] = key;
+            atomicAdd(&h[key & 0xFFu], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 256) hist[size_t{threadIdx.x} * tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// per-tile histogram of the lowest byte of every key. Narrow keys are read a 32-bit word at a time (a tile starts on a word, and the
+// array is padded to whole words: radix_order_layout).
+template <typename K>
+__global__ void __launch_bounds__(kOrderThreads) k_order_hist(const K* keys, uint32_t n, uint32_t tiles, uint32_t* hist) {
+    constexpr uint32_t kPer = 4 / sizeof(K);
+    __shared__ uint32_t h[256];
+    if (threadIdx.x < 256) h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t b = blockIdx.x * uint32_t(kOrderTile), e = min(n, b + uint32_t(kOrderTile));
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(keys + b);
+    const uint32_t words = (e - b + kPer - 1) / kPer;
+    for (uint32_t j = threadIdx.x; j < words; j += uint32_t(kOrderThreads)) {
+        const uint32_t v = w[j];
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k)
+            if (b + j * kPer + k < e) atomicAdd(&h[(v >> (8 * sizeof(K) * k)) & 0xFFu], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 256) hist[size_t{threadIdx.x} * tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// block d: hist[d * tiles + t] = sum of hist[d * tiles + 0..t), hist[256 * tiles + d] = the digit's total
+__global__ void __launch_bounds__(256) k_order_scan(uint32_t* hist, uint32_t tiles) {
+    constexpr int kItems = 8;
+    __shared__ uint32_t wsum[4];
+    uint32_t* h = hist + size_t{blockIdx.x} * tiles;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t run = 0;
+    for (uint32_t c0 = 0; c0 < tiles; c0 += 256 * kItems) {
+        const uint32_t i0 = c0 + threadIdx.x * kItems;
+        uint32_t v[kItems], s = 0;
+#pragma unroll
+        for (int k = 0; k < kItems; ++k) { v[k] = i0 + k < tiles ? h[i0 + k] : 0u; s += v[k]; }
+        uint32_t inc = s;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(inc, d);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        uint32_t at = run + inc - s, total = 0;
+        for (int w = 0; w < 4; ++w) { if (w < wave) at += wsum[w]; total += wsum[w]; }
+#pragma unroll
+        for (int k = 0; k < kItems; ++k) { if (i0 + k < tiles) h[i0 + k] = at; at += v[k]; }
+        run += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) hist[size_t{256} * tiles + blockIdx.x] = run;
+}
+
+// k_radix_scatter for this sort: the digit is the key's lowest byte, the key carried on is `key >> 8` as a KO (KeysOut false: the last
+// pass, nothing is carried), Iota: the first pass, the values are the input positions and `vals` is not read. `hist` is what
+// k_order_scan left. What a block holds in LDS decides how many blocks a CU holds (160 KB: three blocks of at most 52.5 KB), and the
+// scatter runs at the speed of its resident waves, not of memory, so the tile is kept small:
+//   * the digit of a ranked element waits beside the narrow carried key as a byte (a u32 carried on waits whole, its digit in it);
+//   * the first pass keeps a value as its 16-bit position within the tile;
+//   * the per-wave counts, then cursors, are 16-bit halves of a word (a wave owns 1024 keys, a cursor stays below 8192): 4 KB;
+//   * the two 256-entry scans run in the space the values take later, and the table of the write-out in that of the cursors.
+// 44 KB in the first pass of 24-bit keys (u32 -> u16), 52 KB in the second (u16 -> u8), 44 KB in the last.
+template <typename KI, typename KO, bool KeysOut, bool Iota>
+__global__ void __launch_bounds__(kOrderThreads) k_order_scatter(const KI* keys, const uint32_t* vals, KO* keys_out, uint32_t* vals_out, uint32_t n,
+                                                                 uint32_t tiles, const uint32_t* hist) {
+    constexpr int kTile = kOrderTile, kThreads = kOrderThreads, kWaves = kOrderWaves, kSteps = 16;
+    constexpr bool kWholeKey = KeysOut && sizeof(KO) == 4;
+    using V = std::conditional_t<Iota, uint16_t, uint32_t>;
+    __shared__ uint32_t cursor[kWaves][128];                           // digit d of wave w: half d & 1 of cursor[w][d >> 1]
+    __shared__ V sval[kTile];
+    __shared__ KO skey[KeysOut ? kTile : 1];
+    __shared__ uint8_t sdig[kWholeKey ? 1 : kTile];
+    static_assert(sizeof(V) * kTile >= 2 * 256 * sizeof(uint32_t) && sizeof(cursor) >= 256 * sizeof(uint32_t));
+    uint32_t* const part = reinterpret_cast<uint32_t*>(sval);         // dead before the first value is ranked
+    uint32_t* const dpart = part + 256;
+    uint32_t* const delta = &cursor[0][0];                             // written once the cursors are done with
+    const uint32_t blk = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < kWaves * 128; i += kThreads) (&cursor[0][0])[i] = 0;
+    __syncthreads();
+    const uint32_t b = blk * uint32_t(kTile), e = min(n, b + uint32_t(kTile));
+    const uint32_t first = b + wave * uint32_t(kSteps * 64) + lane;
+    uint32_t* mine = cursor[wave];
+    KI key[kSteps]; V val[kSteps];
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        const uint32_t i = first + s * 64;
+        key[s] = 0; val[s] = 0;
+        if (i < e) {
+            key[s] = keys[i];
+            if constexpr (Iota) val[s] = static_cast<V>(i - b); else val[s] = vals[i];
+            const uint32_t d = key[s] & 0xFF;
+            atomicAdd(&mine[d >> 1], 1u << (16 * (d & 1)));
+        }
+    }
+    __syncthreads();
+    uint32_t total = 0, dtotal = 0;
+    if (threadIdx.x < 256) {
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) total += (cursor[w][threadIdx.x >> 1] >> (16 * (threadIdx.x & 1))) & 0xFFFFu;
+        part[threadIdx.x] = total;
+        dtotal = hist[size_t{256} * tiles + threadIdx.x];
+        dpart[threadIdx.x] = dtotal;
+    }
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {                         // inclusive scans: the tile's 256 digit counts, the array's 256 digit totals
+        uint32_t v = 0, dv = 0;
+        if (threadIdx.x < 256 && int(threadIdx.x) >= off) { v = part[threadIdx.x - off]; dv = dpart[threadIdx.x - off]; }
+        __syncthreads();
+        if (threadIdx.x < 256) { part[threadIdx.x] += v; dpart[threadIdx.x] += dv; }
+        __syncthreads();
+    }
+    uint32_t my_delta = 0;
+    if (threadIdx.x < 256) {
+        const uint32_t start = part[threadIdx.x] - total;             // of this digit in the sorted tile
+        // tile-local sorted position j of digit d -> global position j + delta[d] (modulo 2^32)
+        my_delta = (dpart[threadIdx.x] - dtotal) + hist[size_t{threadIdx.x} * tiles + blk] - start;
+        part[threadIdx.x] = start;                                    // (only this thread reads part[threadIdx.x] above)
+    }
+    __syncthreads();
+    if (threadIdx.x < 128) {                                          // counts -> cursors, two digits of a word at a time
+        uint32_t r0 = part[2 * threadIdx.x], r1 = part[2 * threadIdx.x + 1];
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const uint32_t c = cursor[w][threadIdx.x];
+            cursor[w][threadIdx.x] = r0 | (r1 << 16);
+            r0 += c & 0xFFFFu; r1 += c >> 16;
+        }
+    }
+    __syncthreads();
+    const uint64_t below = (uint64_t{1} << lane) - 1;
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        const bool in = first + s * 64 < e;
+        const uint32_t d = key[s] & 0xFF;
+        uint64_t same = __ballot(in);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const uint64_t bal = __ballot((d >> bit) & 1);
+            same &= ((d >> bit) & 1) ? bal : ~bal;
+        }
+        if (in) {
+            const uint32_t rank = __popcll(same & below);
+            const uint32_t at = (mine[d >> 1] >> (16 * (d & 1))) & 0xFFFFu;   // every lane of the group reads before its leader advances the cursor
+            __builtin_amdgcn_wave_barrier();
+            if (rank == 0) atomicAdd(&mine[d >> 1], uint32_t(__popcll(same)) << (16 * (d & 1)));   // (the other half belongs to another group's leader)
+            if constexpr (kWholeKey) skey[at + rank] = key[s];
+            else {
+                if constexpr (KeysOut) skey[at + rank] = static_cast<KO>(key[s] >> 8);
+                sdig[at + rank] = static_cast<uint8_t>(d);
+            }
+            sval[at + rank] = val[s];
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    if (threadIdx.x < 256) delta[threadIdx.x] = my_delta;
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < e - b; j += uint32_t(kThreads)) {
+        if constexpr (kWholeKey) {
+            const KO k = skey[j];
+            const uint32_t at = j + delta[k & 0xFF];
+            keys_out[at] = k >> 8;
+            vals_out[at] = Iota ? b + sval[j] : sval[j];
+        } else {
+            const uint32_t at = j + delta[sdig[j]];
+            if constexpr (KeysOut) keys_out[at] = skey[j];
+            vals_out[at] = Iota ? b + sval[j] : sval[j];
+        }
+    }
+}
+
+// bytes of the key a pass carries on when `left` key bits are still unsorted behind it (0: none)
+inline int order_carry_bytes(int left) { return left <= 0 ? 0 : left <= 8 ? 1 : left <= 16 ? 2 : 4; }
+
+} // namespace
+
+RadixOrderLayout radix_order_layout(uint32_t n, int bits) {
+    const int passes = std::max(1, (bits + 7) / 8);
+    const size_t tiles = (size_t{n} + kOrderTile - 1) / kOrderTile;
+    auto pad = [](size_t words) { return (words + 3) / 4 * 4; };                   // every array starts on 16 bytes
+    RadixOrderLayout l;
+    l.carry = pad(n);                                                              // behind the keys
+    l.vals0 = l.carry + pad((size_t{n} * order_carry_bytes(bits - 8) + 3) / 4);    // (the first pass carries the widest key)
+    l.vals1 = l.vals0 + pad(n);
+    l.hist = l.vals1 + (passes > 1 ? pad(n) : 0);
+    l.words = l.hist + 256 * tiles + 256;
+    return l;
+}
+
+int radix_sort_order(uint32_t* scratch, uint32_t n, int bits, hipStream_t stream, bool first_hist_done, uint32_t** order) {
+    if (bits < 1 || bits > 32) return fail(BVH_AMD_ERR_ARG, "radix_sort_order: 1..32 key bits");
+    const RadixOrderLayout l = radix_order_layout(n, bits);
+    uint32_t* const hist = scratch + l.hist;
+    uint32_t* vbuf[2] = { scratch + l.vals0, scratch + l.vals1 };
+    void* kbuf[2] = { scratch, scratch + l.carry };                               // pass p reads kbuf[p & 1] and writes the other
+    *order = vbuf[0];
+    if (n == 0) return BVH_AMD_OK;
+    const uint32_t tiles = (n + kOrderTile - 1) / kOrderTile;
+    const int passes = (bits + 7) / 8;
+    int in_bytes = 4;
+    for (int p = 0; p < passes; ++p) {
+        const int out_bytes = order_carry_bytes(bits - 8 * (p + 1));
+        const void* kin = kbuf[p & 1]; void* kout = kbuf[(p + 1) & 1];
+        const uint32_t* vin = p == 0 ? nullptr : vbuf[(p + 1) & 1];
+        uint32_t* vout = vbuf[p & 1];
+        const dim3 grid(tiles), block(kOrderThreads);
+        if (!(p == 0 && first_hist_done)) {
+            if (in_bytes == 4) hipLaunchKernelGGL(k_order_hist<uint32_t>, grid, block, 0, stream, static_cast<const uint32_t*>(kin), n, tiles, hist);
+            else if (in_bytes == 2) hipLaunchKernelGGL(k_order_hist<uint16_t>, grid, block, 0, stream, static_cast<const uint16_t*>(kin), n, tiles, hist);
+            else hipLaunchKernelGGL(k_order_hist<uint8_t>, grid, block, 0, stream, static_cast<const uint8_t*>(kin), n, tiles, hist);
+        }
+        hipLaunchKernelGGL(k_order_scan, dim3(256), dim3(256), 0, stream, hist, tiles);
+#define BVH_ORDER_SCATTER(KI, KO, OUT, IOTA) \
+        hipLaunchKernelGGL((k_order_scatter<KI, KO, OUT, IOTA>), grid, block, 0, stream, static_cast<const KI*>(kin), vin, static_cast<KO*>(kout), vout, n, tiles, hist)
+        if (p == 0 && out_bytes == 4) BVH_ORDER_SCATTER(uint32_t, uint32_t, true, true);                  // (the first pass reads u32 keys)
+        else if (p == 0 && out_bytes == 2) BVH_ORDER_SCATTER(uint32_t, uint16_t, true, true);
+        else if (p == 0 && out_bytes == 1) BVH_ORDER_SCATTER(uint32_t, uint8_t, true, true);
+        else if (p == 0) BVH_ORDER_SCATTER(uint32_t, uint8_t, false, true);
+        else if (in_bytes == 4 && out_bytes == 2) BVH_ORDER_SCATTER(uint32_t, uint16_t, true, false);
+        else if (in_bytes == 2 && out_bytes == 1) BVH_ORDER_SCATTER(uint16_t, uint8_t, true, false);
+        else if (in_bytes == 1 && out_bytes == 0) BVH_ORDER_SCATTER(uint8_t, uint8_t, false, false);
+        else return fail(BVH_AMD_ERR_ARG, "radix_sort_order: no kernel for this hand-over of key types");
+#undef BVH_ORDER_SCATTER
+        *order = vout;
+        in_bytes = out_bytes;
+    }
+    BVH_HIP_TRY(hipGetLastError(), BVH_AMD_ERR_HIP);
+    return BVH_AMD_OK;
+}
+
+// test entry (bvh_amd_radix_order_u32): the order of caller-supplied keys through exactly what a reordered launch runs
+int radix_order_of_keys(const uint32_t* d_keys, uint32_t n, int bits, uint32_t* d_order, hipStream_t stream) {
+    if (bits < 1 || bits > 32) return fail(BVH_AMD_ERR_ARG, "radix_order_of_keys: 1..32 key bits");
+    if (n == 0) return BVH_AMD_OK;
+    StreamScope scratch_on(stream);
+    const RadixOrderLayout l = radix_order_layout(n, bits);
+    DevBuf<uint32_t> scratch;
+    BVH_HIP_TRY(scratch.alloc(l.words), BVH_AMD_ERR_HIP);
+    const uint32_t tiles = (n + kOrderTile - 1) / kOrderTile;
+    hipLaunchKernelGGL(k_order_copy_keys, dim3(tiles), dim3(1024), 0, stream, d_keys, n, scratch.p, scratch.p + l.hist, tiles);
+    uint32_t* order = nullptr;
+    if (const int rc = radix_sort_order(scratch.p, n, bits, stream, /*first_hist_done=*/true, &order)) return rc;
+    BVH_HIP_TRY(hipMemcpyAsync(d_order, order, size_t{n} * 4, hipMemcpyDeviceToDevice, stream), BVH_AMD_ERR_HIP);
+    if (!scratch.pooled) BVH_HIP_TRY(hipStreamSynchronize(stream), BVH_AMD_ERR_HIP);   // plain hipFree of the scratch on return
+    return BVH_AMD_OK;
+}
+
 // d_ids: batch * n, overwritten with iota then sorted like std::sort with comp(i, j) = key(a,i) < key(a,j).
 template <typename T>
 int std_sort_ids(uint32_t* d_ids, const T* d_keys, uint32_t n, uint32_t batch, uint32_t astride, uint32_t istride, hipStream_t stream) {

@@ -145,21 +145,29 @@ __global__ void __launch_bounds__(1024) ray_keys_kernel(const T* rays, uint32_t 
 }
 
 // The ticket ranges of a reordered launch, one per XCD, written on the device once the sort has run (one small block; no host
-// synchronisation): range p = the stretch of the sorted order whose keys have the top-three-bit prefix p. `hist` is the sort's
-// scanned histogram of its LAST pass (sort_emul.hip: digit-major, tile-minor, exclusive), so hist[d * tiles] is the first position of
-// digit d and prefix p starts at digit p * digits_per_prefix. With equal slices the last 600-2900 tickets of about half of the
+// synchronisation): range p = the stretch of the sorted order whose keys have the top-three-bit prefix p. `totals` are the 256
+// digit totals the sort's LAST pass has left behind its histogram (sort_emul.hip: radix_sort_order), so digit d starts at the sum of the
+// totals below d, and prefix p starts at digit p * digits_per_prefix. With equal slices the last 600-2900 tickets of about half of the
 // ranges were the first — LONG — rays of the next prefix (the prefixes of a uniform batch hold n / 8 +- a few thousand rays), and the
 // drain of the grid is as long as the longest walk drawn last; with the prefix's own stretch a range ends on its prefix's tail class
 // (ray_key.h). A skewed batch — all origins in one cell, a camera — must not funnel every XCD onto one counter (a single counter
 // costs 2x and more): the prefix boundaries are kept only when EVERY prefix holds between 3/4 and 5/4 of n / parts tickets, otherwise
 // the starts written are the equal slices. The same block zeroes the ticket counters, in place of the launch's memset.
-__global__ void __launch_bounds__(64) ticket_ranges_kernel(const uint32_t* hist, uint32_t tiles, uint32_t digits_per_prefix, uint32_t n, uint32_t parts,
+__global__ void __launch_bounds__(64) ticket_ranges_kernel(const uint32_t* totals, uint32_t digits_per_prefix, uint32_t n, uint32_t parts,
                                                            unsigned long long part_size, uint32_t* starts, unsigned long long* work) {
     const uint32_t p = threadIdx.x;                           // parts <= 32 (launch_planned)
+    uint32_t mine = 0;                                        // the tickets of prefix p
+    if (p < parts) for (uint32_t d = p * digits_per_prefix; d < (p + 1) * digits_per_prefix; ++d) mine += totals[d];
+    uint32_t upto = mine;                                     // inclusive scan over the lanes
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(upto, off);
+        if (int(p) >= off) upto += o;
+    }
     uint32_t begin = n, end = n;
     if (p < parts) {
-        begin = hist[size_t{p} * digits_per_prefix * tiles];
-        if (p + 1 < parts) end = hist[size_t{p + 1} * digits_per_prefix * tiles];
+        begin = upto - mine;
+        if (p + 1 < parts) end = upto;
     }
     const uint32_t even = n / parts, len = end - begin;
     const bool balanced = p >= parts || (begin <= end && end <= n && 4ull * len >= 3ull * even && 4ull * len <= 5ull * even);
@@ -638,9 +646,18 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
     args.parts = t_parts > 0 ? std::min(t_parts, 256) : parts_env > 0 ? std::min(parts_env, 256) : n < 65536 ? 1 : g_last_reordered ? 8 : 32;
     args.part_size = ((n + args.parts - 1) / args.parts + 63) / 64 * 64;
     constexpr size_t kRangeWords = 64;                        // the range starts of a reordered launch live behind the sort's scratch
+    // The key of a reordered launch: how many bits it has decides what the sort carries between its passes, hence its scratch.
+    static const int entry_depth = std::min(29, BVH_DEV_INT("BVH_AMD_RAY_KEY_DEPTH", 0));   // developer experiment
+    static const int cell_bits_env = std::max(1, std::min(8, BVH_DEV_INT("BVH_AMD_RAY_KEY_BITS", 7)));   // developer knob
+    const int cell_bits = t_exp.key_bits > 0 ? std::min(8, t_exp.key_bits) : cell_bits_env;
+    bool entry_keys = false;
+    if constexpr (std::is_same_v<T, float>) entry_keys = entry_depth > 0 && b.dim == 3;
+    const int key_bits = entry_keys ? entry_depth + 3 : 3 * cell_bits + 3;
+    RadixOrderLayout sort_layout{};
     if (g_last_reordered) {
         const uint32_t n32 = static_cast<uint32_t>(n);
-        const size_t words = 4 * n + radix_sort_hist_words(n32, 1) + kRangeWords;   // keys + tmp, indices + tmp, histogram, range starts
+        sort_layout = radix_order_layout(n32, key_bits);
+        const size_t words = sort_layout.words + kRangeWords;   // keys, carried keys, indices + tmp, histogram + digit totals, range starts
         // (from the per-stream block cache the builders use: a stream-ordered allocation per call cost ~20 us of every timed pass)
         hipError_t e = scratch_alloc(&sort_mem, words * sizeof(uint32_t), &sort_tag);
         if (e != hipSuccess) {
@@ -654,7 +671,7 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
         if (const int rc0 = zero_tickets()) return release(rc0);
     } else {
         const uint32_t n32 = static_cast<uint32_t>(n);
-        uint32_t *keys = static_cast<uint32_t*>(sort_mem), *vals = keys + n, *kt = vals + n, *vt = kt + n, *hist = vt + n;
+        uint32_t *keys = static_cast<uint32_t*>(sort_mem), *hist = keys + sort_layout.hist;
         T lo[3], sc[3];
         if (const int rc0 = b.wait_refit()) return release(rc0);      // root_bounds follows a refit_* that changed the boxes on the device
         for (int k = 0; k < 3; ++k) {
@@ -662,19 +679,12 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
             lo[k] = b.root_bounds[2 * k];
             sc[k] = ext > T(0) ? T(64) / ext : T(0);
         }
-        static const int entry_depth = std::min(29, BVH_DEV_INT("BVH_AMD_RAY_KEY_DEPTH", 0));   // developer experiment
-        int key_bits = 21;
-        bool entry_keys = false, first_hist_done = false;
-        if constexpr (std::is_same_v<T, float>) entry_keys = entry_depth > 0 && b.dim == 3;
+        bool first_hist_done = false;
         if constexpr (std::is_same_v<T, float>) {
-            if (entry_keys) {
+            if (entry_keys)
                 hipLaunchKernelGGL(ray_entry_keys_kernel, dim3((n32 + 255) / 256), dim3(256), 0, stream, d_rays, n32, args.pairs, args.root_index, entry_depth, keys);
-                key_bits = entry_depth + 3;
-            }
         }
         if (!entry_keys) {
-            static const int cell_bits_env = std::max(1, std::min(8, BVH_DEV_INT("BVH_AMD_RAY_KEY_BITS", 7)));   // developer knob
-            const int cell_bits = t_exp.key_bits > 0 ? std::min(8, t_exp.key_bits) : cell_bits_env;
             const T rescale = static_cast<T>(1u << cell_bits) / T(64);
             const int class_bits = cell_bits < 3 ? 0 : t_exp.key_class_bits >= 0 ? std::min(3, t_exp.key_class_bits) : (plan && plan->classes) ? 1 : kKeyClassBits;
             g_last_classes = class_bits > 0;
@@ -688,21 +698,20 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
                                sc[2] * rescale, keys, 1u << cell_bits, t_exp.key_curve == 0 ? 0 : cell_bits,      // Hilbert index by default (round 4); "key_curve" 0 = Morton
                                class_bits, class_scale, tail_frac, hist, tiles);
             first_hist_done = true;
-            key_bits = 3 * cell_bits + 3;
         }
         uint32_t* order = nullptr;
-        int rc = radix_sort_pairs<uint32_t>(keys, vals, kt, vt, n32, 1, key_bits, stream, hist, /*iota_vals=*/true, /*keys_wanted=*/false, &order, first_hist_done);
+        int rc = radix_sort_order(keys, n32, key_bits, stream, first_hist_done, &order);
         if (rc) return release(rc);
         args.order = order;
-        // Ticket ranges: one per XCD, each the stretch of ONE key prefix (ticket_ranges_kernel reads the boundaries from the histogram
-        // the sort's last pass has left scanned in `hist`; the last digit holds the key's top key_bits - 8 (passes - 1) bits, so it must
+        // Ticket ranges: one per XCD, each the stretch of ONE key prefix (ticket_ranges_kernel reads the boundaries from the digit
+        // totals the sort's last pass has left behind `hist`; the last digit holds the key's top key_bits - 8 (passes - 1) bits, so it must
         // hold the three prefix bits whole). The kernel also zeroes the ticket counters: the timed pass has as many launches as before.
         const int top_digit_bits = key_bits - 8 * ((key_bits + 7) / 8 - 1);
         const bool align = args.parts == 8 && !args.one_shot && top_digit_bits >= 3 && (t_exp.range_align >= 0 ? t_exp.range_align > 0 : kRangeAlign > 0);
         if (align) {
-            uint32_t* starts = hist + radix_sort_hist_words(n32, 1);
+            uint32_t* starts = keys + sort_layout.words;
             const uint32_t tiles = (n32 + kRadixTileU32 - 1) / kRadixTileU32;
-            hipLaunchKernelGGL(ticket_ranges_kernel, dim3(1), dim3(64), 0, stream, hist, tiles, 1u << (top_digit_bits - 3), n32, args.parts, args.part_size, starts, work);
+            hipLaunchKernelGGL(ticket_ranges_kernel, dim3(1), dim3(64), 0, stream, hist + size_t{256} * tiles, 1u << (top_digit_bits - 3), n32, args.parts, args.part_size, starts, work);
             if (const hipError_t e = hipGetLastError(); e != hipSuccess) return release(fail(BVH_AMD_ERR_HIP, std::string("intersect_rays: ticket_ranges_kernel: ") + hipGetErrorString(e)));
             args.range_starts = starts;
         } else if (const int rc0 = zero_tickets()) return release(rc0);
@@ -759,7 +768,9 @@ static int launch_planned(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, 
 // per ray. (Measuring stretches of ONE batch with different plans was tried first and picks wrongly: a sixteenth of
 // a batch neither fills the persistent grid the same way nor has the ray density per sort key the whole batch has.) Results never
 // depend on the plan. BVH_AMD_CALIBRATE=0 keeps the predictor.
-constexpr float kSortNsPerRay = 0.031f;                    // ray keys + three radix passes: 0.52 ms per 2^24 rays (profiles/r03_*)
+// ray keys + three radix passes. Measured: 0.41 ms per 2^24 rays = 0.024 ns per ray (profiles/r09_bench_ab.jsonl: pass - kernel). The
+// charge stays at the 0.52 ms of profiles/r03_*, on which the plans of the calibrated scenes were settled: it errs against reordering.
+constexpr float kSortNsPerRay = 0.031f;
 
 static uint32_t pack_plan(const Plan& p) { return 1u | (p.reorder ? 2u : 0u) | (p.coop ? 4u : 0u) | (p.classes ? 8u : 0u) | (uint32_t(p.refill) << 8) | (uint32_t(p.leaf) << 16); }
 static Plan unpack_plan(uint32_t w) { return Plan{(w & 2u) != 0, (w & 4u) != 0, int((w >> 8) & 0xFFu), int((w >> 16) & 0xFFu), (w & 8u) != 0}; }
@@ -956,7 +967,7 @@ int prepare_trace(const BvhImpl<T>& b, size_t n_rays_hint, hipStream_t stream) {
         StreamScope scope(stream);
         void* mem = nullptr;
         ScratchTag tag;
-        const size_t words = 4 * n_rays_hint + radix_sort_hist_words(static_cast<uint32_t>(n_rays_hint), 1);
+        const size_t words = radix_order_layout(static_cast<uint32_t>(n_rays_hint), 24).words + 64;   // (launch_planned: the default key has 24 bits)
         if (scratch_alloc(&mem, words * sizeof(uint32_t), &tag) == hipSuccess) scratch_free(mem, tag);
         else (void)hipGetLastError();                         // (no room now: the batch will ask again itself)
     }

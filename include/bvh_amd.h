@@ -771,6 +771,9 @@ BVH_AMD_API int bvh_amd_std_sort_ids3f(const float* d_keys, size_t n, uint32_t* 
 BVH_AMD_API int bvh_amd_std_sort_ids3d(const double* d_keys, size_t n, uint32_t* d_ids_out, void* stream);
 /* stable LSD radix sort of (key, value) pairs by the low `bits` bits of the key, in place */
 BVH_AMD_API int bvh_amd_radix_sort_pairs_u32(uint32_t* d_keys, uint32_t* d_vals, size_t n, int bits, void* stream);
+/* d_order_out[0..n) = the stable order of n < 2^31 keys by their low `bits` bits (1..32), through exactly what a reordered ray or
+ * query batch runs: the first histogram by the key kernel, positions as values, keys narrowed between passes and dropped. */
+BVH_AMD_API int bvh_amd_radix_order_u32(const uint32_t* d_keys, size_t n, int bits, uint32_t* d_order_out, void* stream);
 
 /* Name and average duration source for profiling: the kernel symbol the last intersect call used. */
 BVH_AMD_API const char* bvh_amd_last_kernel_name(void);
