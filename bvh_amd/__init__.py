@@ -12,6 +12,7 @@ Host-side mirror of the reference's interface for the hot path (names follow bvh
     radius_count / radius_search(bvh, prims, points, radius=r, leaf="tri")      (every primitive within r of each point, 3D)
     knn(bvh, prims, points, k, max_distance=inf, leaf="tri") -> ids, dist, counts (the k nearest primitives per point, sorted, 3D)
     overlap_count / overlap_search(bvh, bboxes, query_boxes), self_overlaps(bvh, bboxes) (primitives whose boxes overlap a box; broad phase, 3D)
+    tri_intersect_count / tri_intersect_search(bvh, tris9, query_tris), self_intersections(bvh, tris9) (triangles that intersect a triangle; narrow phase, 3D)
     instance_prepare(geometries, transforms) / intersect_instanced(top, geometries, world2obj, rays) (two-level scenes of placed meshes, 3D)
     tri_bounds / precompute_tris / sphere_bounds                                (Tri::get_bbox, PrecomputedTri)
 
@@ -20,5 +21,5 @@ Everything computes in hand-written HIP kernels through the C-ABI of libbvh_amd.
 """
 from .api import (BinnedSahBuilder, MiniTreeBuilder, SplitHeuristic, Bvh, Config, DefaultBuilder, Quality, RayFlags, SweepSahBuilder, ThreadPool, prepare_trace,  # noqa: F401
                   HITD, HITF, INVALID, NODED, NODEF, NODE2D, NODE2F, closest_points, hits_to_numpy, intersect, precompute_tris, sphere_bounds,
-                  tri_bounds, gather, radius_count, radius_search, offsets_from_counts, ray_hit_count, ray_hits, ray_hits_nearest, RAY_NEAREST_MAX_K, knn, KNN_MAX_K, overlap_count, overlap_search, self_overlaps, instance_prepare, intersect_instanced, std_sort_ids, radix_sort_pairs, radix_order, reinsertion_stats, last_optimize_profile, pinhole_rays, shade_eyelight)
+                  tri_bounds, gather, radius_count, radius_search, offsets_from_counts, ray_hit_count, ray_hits, ray_hits_nearest, RAY_NEAREST_MAX_K, knn, KNN_MAX_K, overlap_count, overlap_search, self_overlaps, tri_intersect_count, tri_intersect_search, self_intersections, instance_prepare, intersect_instanced, std_sort_ids, radix_sort_pairs, radix_order, reinsertion_stats, last_optimize_profile, pinhole_rays, shade_eyelight)
 from ._lib import BvhAmdError  # noqa: F401

@@ -786,6 +786,75 @@ def self_overlaps(bvh: Bvh, bboxes, original_ids: bool = True, counters: bool = 
     return (pairs, out[3]) if counters else pairs
 
 
+_TRI_SKIP_SHARED = 32                                         # BVH_AMD_TRI_SKIP_SHARED
+
+
+def _tri_intersect_args(bvh: Bvh, tris9, query_tris, who: str):
+    """The checks of the triangle-intersection queries: ((n_tris, 9) triangles by original id, (n, 9) query triangles or None)."""
+    if bvh.dim != 3:
+        raise TypeError(f"{who}: 3D trees only")
+    t = bvh._prims_in(tris9, 9, who)
+    q = None if query_tris is None else bvh._prims_in(query_tris, 9, who)
+    return t, q
+
+
+def tri_intersect_count(bvh: Bvh, tris9, query_tris, skip_shared: bool = False, sort_queries=None, counters: bool = False):
+    """For each query triangle, how many of the tree's triangles intersect it (bvh3X_intersect_tris without lists): an int32 (n,)
+    tensor; with counters also (pairs, triangles fetched, leaves). tris9: (n_tris, 9) {p0, p1, p2} indexed by ORIGINAL primitive id,
+    what refit_tris takes; query_tris: (n, 9) in the same layout. Closed sets: touching triangles intersect; a triangle without area
+    or with a NaN or infinite coordinate intersects nothing. skip_shared: pairs with a common vertex are not counted."""
+    torch = _torch()
+    t, q = _tri_intersect_args(bvh, tris9, query_tris, "tri_intersect_count")
+    n = q.shape[0]
+    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_tris")
+    flags = int(_sort_flags(sort_queries)) | (_TRI_SKIP_SHARED if skip_shared else 0)
+    _lib.check(fn(bvh._h, t.data_ptr(), t.shape[0], q.data_ptr(), n, flags, counts.data_ptr(), None, None,
+                  cnt.data_ptr() if counters else None, _stream()), "tri_intersect_count")
+    return (counts, cnt) if counters else counts
+
+
+def tri_intersect_search(bvh: Bvh, tris9, query_tris, max_per_query=None, original_ids: bool = False, skip_shared: bool = False, sort_queries=None,
+                         counters: bool = False):
+    """For each query triangle, the tree's triangles that intersect it (bvh3X_intersect_tris), in the order the tree fixes (depth-first,
+    left child first, ascending index inside a leaf). For a tree built from or refitted to `tris9` this is exactly the brute-force set
+    of the pair test, which decides by signs of determinants only (exact wherever the determinants are, e.g. small integers).
+    Returns (offsets, ids) as overlap_search does: offsets int64 (n + 1,), query q owns ids[offsets[q]:offsets[q + 1]] (int32
+    BVH-order indices, or bvh.prim_ids[i] with original_ids).
+      max_per_query=None: exact lists - a count pass, the offsets on the device, one read of offsets[-1] to size the lists, a fill pass.
+      max_per_query=k: one pass, k slots per query (offsets = k * arange(n + 1)), unused slots holding -1 (INVALID); returns
+        (offsets, ids, counts), counts (int32, untruncated) telling which lists overflowed.
+    With counters, (pairs, triangles fetched, leaves) of the pass that wrote the lists is appended to the result."""
+    t, q = _tri_intersect_args(bvh, tris9, query_tris, "tri_intersect_search")
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_tris")
+    flags = int(_sort_flags(sort_queries, original_ids)) | (_TRI_SKIP_SHARED if skip_shared else 0)
+    n = q.shape[0]
+    call = lambda counts, offsets, ids, _, cnt: fn(bvh._h, t.data_ptr(), t.shape[0], q.data_ptr(), n, flags, counts, offsets, ids, cnt, _stream())
+    out = _two_pass_lists("tri_intersect_search", call, n, q.device, max_per_query, counters)
+    return out[:2] + out[3:]                                                        # (no distances)
+
+
+def self_intersections(bvh: Bvh, tris9, original_ids: bool = True, skip_shared: bool = True, counters: bool = False):
+    """Every unordered pair of the tree's triangles that intersect, once (bvh3X_intersect_tris_self): a mesh's self-intersections. An
+    (m, 2) int64 device tensor shaped as self_overlaps returns it; with original_ids both columns hold original primitive ids (rows of
+    `tris9`), otherwise BVH-order indices with first < second. skip_shared (the default): pairs with a common vertex, a mesh's own
+    neighbours, are left out. With counters, (pairs, triangles fetched, leaves) of the fill pass is returned too."""
+    torch = _torch()
+    t, _ = _tri_intersect_args(bvh, tris9, None, "self_intersections")
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_tris_self")
+    n = bvh.prim_count
+    flags = (8 if original_ids else 0) | (_TRI_SKIP_SHARED if skip_shared else 0)
+    call = lambda counts, offsets, ids, _, cnt: fn(bvh._h, t.data_ptr(), t.shape[0], flags, counts, offsets, ids, cnt, _stream())
+    out = _two_pass_lists("self_intersections", call, n, t.device, None, counters)
+    offsets, ids = out[0], out[1]
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=t.device), offsets[1:] - offsets[:-1])
+    if original_ids:
+        rows = bvh.device_prim_ids().long()[rows]
+    pairs = torch.stack([rows, ids.long()], dim=1)
+    return (pairs, out[3]) if counters else pairs
+
+
 def _geometry_table(geometries, who: str):
     """(struct bvh_amd_geometry3X array, family suffix, torch dtype, what keeps the triangle tensors alive) of a list of (Bvh, prims12)."""
     torch = _torch()

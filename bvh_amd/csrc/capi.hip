@@ -590,6 +590,18 @@ int overlap(const typename Family<T, 3>::Bvh* bvh, bool self, const T* d_bboxes,
                              static_cast<hipStream_t>(stream));
 }
 
+// bvh3X_intersect_tris / bvh3X_intersect_tris_self: d_queries9 = NULL and n = the tree's primitive count in self mode.
+template <typename T>
+int intersect_tris(const typename Family<T, 3>::Bvh* bvh, bool self, const T* d_tris9, size_t n_tris, const T* d_queries9, size_t n, unsigned flags,
+                   uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, bvh_amd_counters* d_counters, void* stream)
+{
+    const char* who = self ? "intersect_tris_self" : "intersect_tris";
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, self ? 1 : n, who, &b)) return rc;
+    return launch_tri_intersect<T>(*b, self, d_tris9, n_tris, d_queries9, self ? b->prim_count : n, flags, d_counts, d_offsets, d_list_prims, d_counters,
+                                   static_cast<hipStream_t>(stream));
+}
+
 // bvh3X_instance_prepare / bvh3X_intersect_rays_instanced: struct bvh_amd_geometry3X is GeomRef<T> by layout (a handle is its BvhImpl).
 template <typename T, typename Geometry>
 const GeomRef<T>* geom_refs(const Geometry* geoms) {
@@ -842,6 +854,12 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_overlap_self(const bvh##S* b, const T* bboxes, size_t n_boxes, unsigned flags, uint32_t* counts,        \
                               const uint64_t* offsets, uint32_t* list_prims, bvh_amd_counters* cnt, void* s) {           \
         return overlap<T>(b, true, bboxes, n_boxes, nullptr, 0, flags, counts, offsets, list_prims, cnt, s); }                  \
+    int bvh##S##_intersect_tris(const bvh##S* b, const T* tris9, size_t n_tris, const T* queries9, size_t n, unsigned flags, uint32_t* counts, \
+                                const uint64_t* offsets, uint32_t* list_prims, bvh_amd_counters* cnt, void* s) {         \
+        return intersect_tris<T>(b, false, tris9, n_tris, queries9, n, flags, counts, offsets, list_prims, cnt, s); }   \
+    int bvh##S##_intersect_tris_self(const bvh##S* b, const T* tris9, size_t n_tris, unsigned flags, uint32_t* counts,   \
+                                     const uint64_t* offsets, uint32_t* list_prims, bvh_amd_counters* cnt, void* s) {    \
+        return intersect_tris<T>(b, true, tris9, n_tris, nullptr, 0, flags, counts, offsets, list_prims, cnt, s); }     \
     int bvh##S##_instance_prepare(const bvh_amd_geometry##S* geoms, size_t n_geoms, const T* obj2world, const uint32_t* geometry,  \
                                   size_t n_instances, T* world2obj, T* bboxes, T* centers, void* s) {                    \
         return launch_instance_prepare<T>(geom_refs<T>(geoms), n_geoms, obj2world, geometry, n_instances, world2obj, bboxes, centers, \

@@ -278,6 +278,12 @@ int offsets_from_counts(const uint32_t* d_counts, size_t n, uint64_t* d_offsets,
 template <typename T>
 int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_boxes, const T* d_queries6, size_t n, unsigned flags, uint32_t* d_counts,
                    const uint64_t* d_offsets, uint32_t* d_list_prims, bvh_amd_counters* d_counters, hipStream_t stream);
+// tri_intersect.hip: batched triangle-intersection queries, n x {p0.xyz, p1.xyz, p2.xyz} against d_tris9[prim_ids[i]] (n_tris triangles by
+// original id), output as launch_overlap (flags: ORIGINAL_IDS, SORTED, UNSORTED, TRI_SKIP_SHARED); self: the queries are the tree's own
+// triangles, d_queries9 is unused, n = prim_count, primitive q lists only i > q (flags: ORIGINAL_IDS, TRI_SKIP_SHARED)
+template <typename T>
+int launch_tri_intersect(const BvhImpl<T>& b, bool self, const T* d_tris9, size_t n_tris, const T* d_queries9, size_t n, unsigned flags, uint32_t* d_counts,
+                         const uint64_t* d_offsets, uint32_t* d_list_prims, bvh_amd_counters* d_counters, hipStream_t stream);
 // ray_hits.hip: batched all-hits ray queries, n x {org, dir, tmin, tmax} -> per ray the count of primitives the unshortened ray crosses
 // and, with d_offsets, their hit records in the ray's segment [offsets[r], offsets[r + 1]) (flags: ROBUST, ORIGINAL_IDS, SORTED, UNSORTED)
 template <typename T>

@@ -49,7 +49,8 @@ int point_query_check(const BvhImpl<T>& b, size_t n, unsigned flags, bool requir
 // kinds share, deep_d2 the spill's other array (entry - 4 bytes per entry; null for a shallow tree). Owns the scratch behind both.
 // kQueryBoxes (overlap.hip): a query is a box of 6 scalars, ordered by the cell of its centre; d_queries may then be null when the batch is
 // not reordered (self mode: the lanes take their boxes from d_prims). kQueryRays (ray_hits.hip): a query is a ray of 8 scalars, ordered
-// by the cell of its origin and the octant of its direction.
+// by the cell of its origin and the octant of its direction. kQueryTris (tri_intersect.hip): a query is a triangle of 9 scalars, ordered by the
+// cell of its box's centre; self mode as for kQueryBoxes.
 template <typename T, int Kind = kQueryPoints, typename Launch>
 int point_query_run(const BvhImpl<T>& b, const T* d_prims, const T* d_queries, size_t n, unsigned flags, bvh_amd_counters* d_counters, size_t entry,
                     size_t lanes, size_t sort_min, int key_bits, const char* who, hipStream_t stream, Launch launch) {

@@ -328,6 +328,8 @@ template <> struct Api<float, 3> {
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_boxes(h, static_cast<const float*>(bb), nb, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_self(h, static_cast<const float*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
+    static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_intersect_tris(h, static_cast<const float*>(t9), nt, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
+    static int intersect_tris_self(const Handle* h, const void* t9, size_t nt, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_intersect_tris_self(h, static_cast<const float*>(t9), nt, f, counts, offsets, list, nullptr, nullptr); }
     using CGeometry = bvh_amd_geometry3f;
     static int instance_prepare(const CGeometry* g, size_t ng, const void* m, const uint32_t* gid, size_t n, void* w, void* bb, void* cc) { return bvh3f_instance_prepare(g, ng, static_cast<const float*>(m), gid, n, static_cast<float*>(w), static_cast<float*>(bb), static_cast<float*>(cc), nullptr); }
     static int trace_instanced(const Handle* top, const CGeometry* g, size_t ng, const void* w, const uint32_t* gid, size_t n, const void* rays, size_t nr, unsigned f, void* hits, uint32_t* inst) { return bvh3f_intersect_rays_instanced(top, g, ng, static_cast<const float*>(w), gid, n, static_cast<const bvh_ray3f*>(rays), nr, f, static_cast<bvh_hit3f*>(hits), inst, nullptr, nullptr); }
@@ -375,6 +377,8 @@ template <> struct Api<double, 3> {
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_boxes(h, static_cast<const double*>(bb), nb, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_self(h, static_cast<const double*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
+    static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_intersect_tris(h, static_cast<const double*>(t9), nt, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
+    static int intersect_tris_self(const Handle* h, const void* t9, size_t nt, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_intersect_tris_self(h, static_cast<const double*>(t9), nt, f, counts, offsets, list, nullptr, nullptr); }
     using CGeometry = bvh_amd_geometry3d;
     static int instance_prepare(const CGeometry* g, size_t ng, const void* m, const uint32_t* gid, size_t n, void* w, void* bb, void* cc) { return bvh3d_instance_prepare(g, ng, static_cast<const double*>(m), gid, n, static_cast<double*>(w), static_cast<double*>(bb), static_cast<double*>(cc), nullptr); }
     static int trace_instanced(const Handle* top, const CGeometry* g, size_t ng, const void* w, const uint32_t* gid, size_t n, const void* rays, size_t nr, unsigned f, void* hits, uint32_t* inst) { return bvh3d_intersect_rays_instanced(top, g, ng, static_cast<const double*>(w), gid, n, static_cast<const bvh_ray3d*>(rays), nr, f, static_cast<bvh_hit3d*>(hits), inst, nullptr, nullptr); }
@@ -1061,6 +1065,47 @@ void overlap_self_batch(const Bvh<Node>& bvh, const DeviceArray<BBox<typename No
     static_assert(Node::dimension == 3, "overlap queries: 3D trees only");
     detail::overlap_host([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
         return Api<T, 3>::overlap_self(bvh.device(), bboxes.data(), bboxes.size(), flags, c, o, l); }, bvh.prim_ids.size(), offsets, list_prims, "overlap_self");
+}
+
+// For each query triangle, every triangle of the tree that intersects it (include/bvh_amd.h: bvh3X_intersect_tris), in the order the
+// tree fixes: closed sets, decided by signs of determinants only (exact wherever these are), exact for a tree built from or refitted
+// to `tris`. `tris` is indexed by ORIGINAL primitive id, like refit_tris'. The outputs, the device and host forms and `flags` are those
+// of overlap_boxes_batch, with BVH_AMD_TRI_SKIP_SHARED to leave out pairs that have a vertex in common.
+// intersect_tris_self_batch: the queries are the tree's own triangles, row q lists only i > q, so the CSR (offsets, list) is the list
+// of unordered intersecting pairs, each once: a mesh's self-intersections (with BVH_AMD_TRI_SKIP_SHARED: without its neighbours).
+template <typename Node>
+void intersect_tris_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, const DeviceArray<Tri<typename Node::Scalar, 3>>& queries,
+                          DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "triangle-intersection queries: 3D trees only");
+    detail::overlap_device([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
+        return Api<T, 3>::intersect_tris(bvh.device(), tris.data(), tris.size(), queries.data(), queries.size(), flags, c, o, l); }, queries.size(), counts, offsets, list_prims, "intersect_tris");
+}
+// Host form: exact lists. Query q's triangles are list_prims[offsets[q] .. offsets[q + 1]).
+template <typename Node>
+void intersect_tris_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, std::span<const Tri<typename Node::Scalar, 3>> queries,
+                          std::vector<uint64_t>& offsets, std::vector<uint32_t>& list_prims, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "triangle-intersection queries: 3D trees only");
+    DeviceArray<Tri<T, 3>> d_queries(queries);
+    detail::overlap_host([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
+        return Api<T, 3>::intersect_tris(bvh.device(), tris.data(), tris.size(), d_queries.data(), queries.size(), flags, c, o, l); }, queries.size(), offsets, list_prims, "intersect_tris");
+}
+template <typename Node>
+void intersect_tris_self_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, DeviceArray<uint32_t>* counts,
+                               const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "triangle-intersection queries: 3D trees only");
+    detail::overlap_device([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
+        return Api<T, 3>::intersect_tris_self(bvh.device(), tris.data(), tris.size(), flags, c, o, l); }, bvh.prim_ids.size(), counts, offsets, list_prims, "intersect_tris_self");
+}
+template <typename Node>
+void intersect_tris_self_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, std::vector<uint64_t>& offsets,
+                               std::vector<uint32_t>& list_prims, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "triangle-intersection queries: 3D trees only");
+    detail::overlap_host([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
+        return Api<T, 3>::intersect_tris_self(bvh.device(), tris.data(), tris.size(), flags, c, o, l); }, bvh.prim_ids.size(), offsets, list_prims, "intersect_tris_self");
 }
 
 // For each ray, every primitive the UNSHORTENED ray crosses (include/bvh_amd.h: bvh3X_intersect_rays_all_*): what Bvh::intersect<false,

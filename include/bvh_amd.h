@@ -118,8 +118,10 @@ enum bvh_amd_ray_flags {
                                   >= 100 records (sum of area(node) / area(root) over the inner nodes): +40..50 % there      */
     BVH_AMD_RAY_UNSORTED = 16u, /* never reorder (rays already coherent, or no scratch memory to spare: 16 bytes per ray)  */
                                 /* (SORTED / UNSORTED / ORIGINAL_IDS apply to bvhXX_closest_points_* and bvhXX_radius_search_* queries too) */
-    BVH_AMD_RAY_ORIGINAL_IDS = 8u  /* hit.prim = the ORIGINAL primitive id bvh.prim_ids[i] (what c_api_example.c:265-268 looks up per
+    BVH_AMD_RAY_ORIGINAL_IDS = 8u, /* hit.prim = the ORIGINAL primitive id bvh.prim_ids[i] (what c_api_example.c:265-268 looks up per
                                       hit) instead of the BVH-order index i: one more pass over the hit records, on the device    */
+    BVH_AMD_TRI_SKIP_SHARED = 32u  /* bvh3X_intersect_tris / bvh3X_intersect_tris_self only (every other entry point refuses it): a
+                                      pair of triangles with a common vertex is not listed                                       */
 };
 
 /* Which reference builder a device build reproduces (bit-exact node/prim order). */
@@ -607,8 +609,9 @@ BVH_AMD_API int bvh3d_knn_sphere(const struct bvh3d*, const double* d_sph4, cons
  * scalar, d_offsets and d_counters 8 bytes, d_counts and d_list_prims 4. Refused with BVH_AMD_ERR_ARG: a 2D tree, a NULL handle, a NULL
  * or misaligned pointer, the forbidden output combinations, a tree without a device copy or without device prim ids, n_boxes at or
  * below the largest prim id. Re-entrant on a const tree (no work slot is claimed); like every reader of the tree, the caller orders
- * it after a bvhXX_refit_*. Not offered: the 2D families, exact primitive-against-box tests (triangle SAT, sphere against box: that
- * narrow phase is the caller's), a dual-tree (tree against tree) traversal, a fused single-walk list variant. */
+ * it after a bvhXX_refit_*. Not offered: the 2D families, exact primitive-against-box tests (sphere against box: that narrow phase
+ * is the caller's; for triangles against triangles see bvh3X_intersect_tris below), a dual-tree (tree against tree) traversal, a
+ * fused single-walk list variant. */
 BVH_AMD_API int bvh3f_overlap_boxes(const struct bvh3f*, const float* d_bboxes, size_t n_boxes, const float* d_queries6, size_t n, unsigned flags,
     uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
 BVH_AMD_API int bvh3d_overlap_boxes(const struct bvh3d*, const double* d_bboxes, size_t n_boxes, const double* d_queries6, size_t n, unsigned flags,
@@ -616,6 +619,54 @@ BVH_AMD_API int bvh3d_overlap_boxes(const struct bvh3d*, const double* d_bboxes,
 BVH_AMD_API int bvh3f_overlap_self(const struct bvh3f*, const float* d_bboxes, size_t n_boxes, unsigned flags,
     uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
 BVH_AMD_API int bvh3d_overlap_self(const struct bvh3d*, const double* d_bboxes, size_t n_boxes, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
+
+/* ---- batched triangle-intersection queries and mesh self-intersections (narrow phase) ---------------------------------------------- */
+/* d_tris9 is the array bvh3X_refit_tris takes: n_tris x {p0.xyz, p1.xyz, p2.xyz}, indexed by ORIGINAL primitive id; the triangle of
+ * BVH-order primitive i is d_tris9[prim_ids[i]]. n_tris must exceed the largest prim id. d_queries9 is n x 9 scalars in the same layout.
+ *   test:    two triangles intersect iff they share a point as CLOSED sets: touching at a vertex or along an edge counts, and so does
+ *            coplanar containment. The decision is taken from SIGNS of determinants of coordinate differences only: the side of a
+ *            vertex against the other triangle's plane ((v - p0) . n, n = (p1 - p0) x (p2 - p0)), 3 x 3 determinants of differences
+ *            that order the two triangles' intervals on the line their planes share, and for coplanar triangles 2 x 2 orientations in
+ *            the projection along the largest component of the query's normal. No division, no square root, no epsilon, no product
+ *            of two determinants: whenever every determinant is computed without rounding (small integers, say) the answer is the
+ *            exact one; otherwise it is the one these roundings give (one rounding per operation, no contraction), the same on the
+ *            device and in a host build of the same source. Before the signs, the boxes of the two triangles are compared (closed
+ *            intervals): boxes apart, no intersection.
+ *   invalid: a triangle whose computed normal is (0, 0, 0) (no area), or has a NaN or infinite component (a NaN or infinite
+ *            coordinate ends there), intersects nothing: as a query it has an empty list, as a primitive it is never listed. -0 = +0.
+ *   result:  every BVH-order index i whose triangle intersects the query's and all of whose ancestors' boxes overlap the box of the
+ *            query triangle (the node test of bvh3X_overlap_boxes, closed intervals). For a tree fitted to these triangles (built from
+ *            bvh_amd_tri_bounds3X of them, or bvh3X_refit_tris with them) that is EXACTLY the brute-force set of the pair test. For
+ *            triangles the tree was not fitted to it is the walk's set.
+ *   order, output: those of bvh3X_overlap_boxes: depth-first, left child before right, ascending index inside a leaf; d_counts[q] is
+ *            never truncated; query q owns [d_offsets[q], d_offsets[q + 1]) of d_list_prims (required iff d_offsets), the rest of a
+ *            segment is padded with BVH_AMD_INVALID, nothing outside a segment is written, a non-ascending segment is empty. At least
+ *            one of d_counts and d_offsets must be given.
+ *   self:    bvh3X_intersect_tris_self takes no queries: n = bvhXX_get_prim_count, query q IS BVH-order primitive q with the triangle
+ *            d_tris9[prim_ids[q]], and its list holds only i > q (compared in BVH order): every unordered intersecting pair appears
+ *            exactly once and no triangle pairs with itself. Self mode never reorders: BVH_AMD_RAY_SORTED and BVH_AMD_RAY_UNSORTED are
+ *            refused there.
+ *   flags:   BVH_AMD_RAY_ORIGINAL_IDS lists prim_ids[i] (the order and the i > q filter stay BVH-order). BVH_AMD_TRI_SKIP_SHARED (both
+ *            entry points): a pair in which some vertex of one triangle equals some vertex of the other on all three coordinates
+ *            (==: -0 equals +0, a NaN equals nothing) is not listed; without it the neighbours of a mesh's triangle fill its self
+ *            list. For bvh3X_intersect_tris, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED: the reordering key is the Hilbert cell of the
+ *            centre of the query triangle's box in the root box (with neither, batches of >= 1M queries are reordered). Any other bit:
+ *            BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * Outputs are in caller order. A query's result does not depend on batch size, position, order, flags, stream or thread. d_counters
+ * (optional) receives {pair records fetched, triangles fetched (in self mode after the i > q filter; before any box or shared-vertex
+ * early-out), leaves visited}. Alignment: d_tris9 and d_queries9 to their scalar, d_offsets and d_counters 8 bytes, d_counts and
+ * d_list_prims 4. Refused with BVH_AMD_ERR_ARG: a 2D tree, a NULL handle, a NULL or misaligned pointer, the forbidden output
+ * combinations, a tree without a device copy or without device prim ids, n_tris at or below the largest prim id. Re-entrant on a const
+ * tree (no work slot is claimed); like every reader of the tree, the caller orders it after a bvhXX_refit_*. Not offered: the segment
+ * two triangles share, spheres, the 2D families, a dual-tree traversal, exact arithmetic beyond what the inputs make exact. */
+BVH_AMD_API int bvh3f_intersect_tris(const struct bvh3f*, const float* d_tris9, size_t n_tris, const float* d_queries9, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_intersect_tris(const struct bvh3d*, const double* d_tris9, size_t n_tris, const double* d_queries9, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_intersect_tris_self(const struct bvh3f*, const float* d_tris9, size_t n_tris, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_intersect_tris_self(const struct bvh3d*, const double* d_tris9, size_t n_tris, unsigned flags,
     uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
 
 /* ---- batched all-hits ray queries: for each ray, every primitive it crosses --------------------------------------------------------- */
