@@ -1,9 +1,10 @@
-// Per-lane body of the batched closest-point query (closest.hip): the depth-first walk of one query through the pair records. The
-// query load, the distance functions and the stack's index arithmetic are point_walk.inc's. Kept as an include so that tests/cpp/closest_body_host.cpp
+// Per-lane body of the batched closest-point query (closest.hip): one query's load, its two tests and its record around
+// nearest_walk.inc, the pruned depth-first walk through the pair records that knn_body.inc and ray_nearest_body.inc also run. The query
+// load and the distance functions are point_walk.inc's. Kept as an include so that tests/cpp/closest_body_host.cpp
 // compiles the very same text for the host (one emulated lane per query). Expects what point_walk.inc expects, and store_hit.
 #pragma once
 
-#include "point_walk.inc"
+#include "nearest_walk.inc"
 
 namespace bvh_amd {
 
@@ -21,8 +22,8 @@ struct ClosestArgs : PointArgs<T> {
     T* deep_d2;                                // Deep kernels only: beside deep_nodes
 };
 
-// One query, one lane: depth-first walk, nearer child first, the farther one pushed with its box distance^2; a child or popped entry
-// farther than the best primitive so far is dropped. best starts at max_distance^2; among the primitives the walk TESTS, the lowest
+// One query, one lane: nearest_walk keyed by box distance^2 with `best` as its limit: nearer child first, the farther one pushed with
+// its key; a child or popped entry farther than the best primitive so far is dropped. best starts at max_distance^2; among the primitives the walk TESTS, the lowest
 // BVH-order index of those at the smallest computed squared distance wins, whatever the visiting order. A subtree is skipped when
 // its box's computed distance^2 exceeds `best`, so a primitive whose computed distance rounds below its own leaf box's (a sphere's
 // (fl(sqrt(s)) - r)^2 against the box's exact s; a triangle with area) can hide one at an equal or one-ulp-nearer distance in another
@@ -39,57 +40,16 @@ __device__ inline void closest_lane(const ClosestArgs<T>& a, unsigned long long 
     uint32_t best_prim = BVH_AMD_INVALID;
     T best = max_d * max_d, best_u = T(0), best_v = T(0);
 
-    uint32_t spill_node[kPointSmall - kClosestLds];
-    T spill_d2[kPointSmall - kClosestLds];
-    uint32_t sp = 0;
-    auto push = [&](uint32_t node, T d2) {
-        if (sp < kClosestLds) { lds_node[sp * kBlock + tid] = node; lds_d2[sp * kBlock + tid] = d2; }
-        else if (!Deep || sp < kPointSmall) { const uint32_t i = stack_small_at<kClosestLds>(sp); spill_node[i] = node; spill_d2[i] = d2; }
-        else { const unsigned long long i = stack_deep_at(a, lane, sp); a.deep_nodes[i] = node; a.deep_d2[i] = d2; }
-        ++sp;
-    };
-    // the next stacked entry that can still hold something nearer than `best` (false: the walk is over)
-    auto pop = [&](uint32_t& node) -> bool {
-        while (sp > 0) {
-            --sp;
-            uint32_t e;
-            T d2;
-            if (sp < kClosestLds) { e = lds_node[sp * kBlock + tid]; d2 = lds_d2[sp * kBlock + tid]; }
-            else if (!Deep || sp < kPointSmall) { const uint32_t i = stack_small_at<kClosestLds>(sp); e = spill_node[i]; d2 = spill_d2[i]; }
-            else { const unsigned long long i = stack_deep_at(a, lane, sp); e = a.deep_nodes[i]; d2 = a.deep_d2[i]; }
-            if (d2 <= best) { node = e; return true; }
-        }
-        return false;
-    };
-
-    uint32_t node = a.root_index;
-    bool live = valid;
-    while (live) {
-        while ((node & kCountMask) == 0) {                    // inner node: both children in one record
-            T lb[6], rb[6];
-            uint32_t li = 0, ri = 0;
-            load_pair(a.pairs + (node >> (kCountBits + 1)), lb, rb, li, ri);
-            if (Stats) ++cnt[0];
-            const T dl = box_dist2(lb, q), dr = box_dist2(rb, q);
-            const bool hl = dl <= best, hr = dr <= best;
-            if (hl && hr) {
-                if (dr < dl) { push(li, dl); node = ri; }
-                else { push(ri, dr); node = li; }
-            } else if (hl) node = li;
-            else if (hr) node = ri;
-            else if (!pop(node)) { live = false; break; }
-        }
-        if (!live) break;
-        const uint32_t first = node >> kCountBits, count = node & kCountMask;
-        if (Stats) ++cnt[2];
-        for (uint32_t i = first; i < first + count; ++i) {
-            if (Stats) ++cnt[1];
+    nearest_walk<T, kClosestLds, Stats, Deep>(a, valid, lds_node, lds_d2, uint32_t(kBlock), tid, lane, a.deep_d2, best, cnt,
+        [&](const T (&lb)[6], const T (&rb)[6], T& dl, T& dr, bool& hl, bool& hr) {
+            dl = box_dist2(lb, q); dr = box_dist2(rb, q);
+            hl = dl <= best; hr = dr <= best;
+        },
+        [&](uint32_t i) {
             T u = T(0), v = T(0);
             const T d2 = leaf_dist2<T, Leaf>(a.prims, i, q, u, v);
             if (d2 < best || (d2 == best && i < best_prim)) { best = d2; best_prim = i; best_u = u; best_v = v; }
-        }
-        live = pop(node);
-    }
+        });
     if (best_prim != BVH_AMD_INVALID) {
         store_hit(a.hits + qi, a.prim_ids ? a.prim_ids[best_prim] : best_prim, Num<T>::sqrt_(best), best_u, best_v);
     } else {

@@ -6,8 +6,12 @@
 // The distance functions are point_walk.inc's (tri_dist2 / sphere_dist2 / box_dist2), so a distance is exactly what closest_points
 // measures, and the walk is closest_lane's with the best distance replaced by the worst of the k held: k = 1 gives closest_points'
 // primitive, distance and counters. Kept as an include so that tests/cpp/knn_body_host.cpp compiles the very same text for the host
-// (one emulated lane per query). The candidate heap and its LDS layout are knn_heap.inc (shared with ray_nearest_body.inc). Expects
-// what point_walk.inc expects.
+// (one emulated lane per query). The candidate set, its two operations and its LDS layout are knn_heap.inc (shared with
+// ray_nearest_body.inc). Expects what point_walk.inc expects.
+// The walk below is a COPY of nearest_walk.inc's text (the stack, push / pop, the descent, the leaf loop), which closest_lane and
+// ray_nearest_lane call: knn_lane built on that function computes the same bytes, but every float-triangle row of tools/knn_bench.py
+// came out 1 - 3.5 % slower in each of two alternated runs (DESIGN.md, "Nearest queries: the one walk": same instructions, another
+// packing of the two box distances and other registers), so this kind keeps its text. A fix to one belongs in the other.
 #pragma once
 
 #include "point_walk.inc"
@@ -29,10 +33,9 @@ struct KnnArgs : PointArgs<T> {
 // One query, one lane: closest_lane's walk — depth-first, nearer child first (ties left), the farther one pushed with its box
 // distance^2 — pruned against `worst`: max_distance^2 until k candidates are held, then the d2 of the largest (d2, index) held. A
 // child or a popped entry is kept iff its box distance^2 <= worst (not <: a primitive at the same distance with a lower index
-// stays reachable wherever its box is not computed farther than `worst`). Inside a leaf the index ascends; a primitive is accepted
-// while fewer than k are held iff d2 <= max_distance^2,
-// afterwards iff (d2, index) is below the largest held, which it replaces. The candidates are appended unordered until the k-th
-// makes them a max-heap; a replacement is one sift-down; at the end an in-place heapsort leaves them ascending, and the row is
+// stays reachable wherever its box is not computed farther than `worst`). Inside a leaf the index ascends; a primitive is offered
+// to the candidate set (knn_offer): while fewer than k are held it is taken iff d2 <= max_distance^2, afterwards iff (d2, index) is
+// below the largest held, which it replaces. At the end knn_sort leaves the candidates ascending, and the row is
 // written: nothing is stored while walking, so an invalid query still pads its row. Slot `slot` of the launch (query order[slot], or
 // slot itself); `lane` indexes the HBM spill (Deep), `tid` and `stride` the LDS arrays. cnt += {pair records fetched, primitives
 // tested, leaves visited}.
@@ -44,7 +47,7 @@ __device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, co
     const bool valid = load_query(a, slot, qi, q, max_d);    // NaN coordinates / radius, negative radius: empty row
     const T r2 = max_d * max_d;
     const uint32_t k = a.k;
-    T* const cand_d2 = lds.cand_d2;
+    T* const cand_d2 = lds.cand_key;
     uint32_t* const cand_id = lds.cand_id;
     T worst = r2;                                             // the pruning distance^2
     uint32_t worst_id = BVH_AMD_INVALID;                      // the index beside it, once k are held
@@ -54,7 +57,7 @@ __device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, co
     T spill_d2[kPointSmall - kKnnLds];
     uint32_t sp = 0;
     auto push = [&](uint32_t node, T d2) {
-        if (sp < kKnnLds) { lds.stack_node[sp * stride + tid] = node; lds.stack_d2[sp * stride + tid] = d2; }
+        if (sp < kKnnLds) { lds.stack_node[sp * stride + tid] = node; lds.stack_key[sp * stride + tid] = d2; }
         else if (!Deep || sp < kPointSmall) { const uint32_t i = stack_small_at<kKnnLds>(sp); spill_node[i] = node; spill_d2[i] = d2; }
         else { const unsigned long long i = stack_deep_at(a, lane, sp); a.deep_nodes[i] = node; a.deep_d2[i] = d2; }
         ++sp;
@@ -65,7 +68,7 @@ __device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, co
             --sp;
             uint32_t e;
             T d2;
-            if (sp < kKnnLds) { e = lds.stack_node[sp * stride + tid]; d2 = lds.stack_d2[sp * stride + tid]; }
+            if (sp < kKnnLds) { e = lds.stack_node[sp * stride + tid]; d2 = lds.stack_key[sp * stride + tid]; }
             else if (!Deep || sp < kPointSmall) { const uint32_t i = stack_small_at<kKnnLds>(sp); e = spill_node[i]; d2 = spill_d2[i]; }
             else { const unsigned long long i = stack_deep_at(a, lane, sp); e = a.deep_nodes[i]; d2 = a.deep_d2[i]; }
             if (d2 <= worst) { node = e; return true; }
@@ -97,31 +100,12 @@ __device__ inline void knn_lane(const KnnArgs<T>& a, unsigned long long slot, co
             if (Stats) ++cnt[1];
             T u = T(0), v = T(0);
             const T d2 = leaf_dist2<T, Leaf>(a.prims, i, q, u, v);
-            if (held < k) {
-                if (d2 <= r2) {
-                    cand_d2[held * stride + tid] = d2;
-                    cand_id[held * stride + tid] = i;
-                    if (++held == k) {
-                        knn_make_heap(cand_d2, cand_id, stride, tid, k);
-                        worst = cand_d2[tid]; worst_id = cand_id[tid];
-                    }
-                }
-            } else if (knn_less(d2, i, worst, worst_id)) {
-                knn_sift_down(cand_d2, cand_id, stride, tid, 0u, k, d2, i);
-                worst = cand_d2[tid]; worst_id = cand_id[tid];
-            }
+            knn_offer(cand_d2, cand_id, stride, tid, k, held, worst, worst_id, d2, i, d2 <= r2);
         }
         live = pop(node);
     }
 
-    // ascending (d2, index): heapsort in place
-    if (held < k) knn_make_heap(cand_d2, cand_id, stride, tid, held);
-    for (uint32_t m = held; m-- > 1;) {
-        const T ld = cand_d2[m * stride + tid], td = cand_d2[tid];
-        const uint32_t li = cand_id[m * stride + tid], ti = cand_id[tid];
-        cand_d2[m * stride + tid] = td; cand_id[m * stride + tid] = ti;
-        knn_sift_down(cand_d2, cand_id, stride, tid, 0u, m, ld, li);
-    }
+    knn_sort(cand_d2, cand_id, stride, tid, k, held);         // ascending (d2, index)
     uint32_t* const row_prims = a.out_prims + qi * k;
     T* const row_dist = a.out_dist ? a.out_dist + qi * k : nullptr;
     for (uint32_t j = 0; j < held; ++j) {

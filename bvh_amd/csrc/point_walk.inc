@@ -1,5 +1,5 @@
-// What the per-lane bodies of the point and box queries share (closest_body.inc, knn_body.inc, and through list_walk.inc
-// radius_body.inc and overlap_body.inc): the arguments common to their kernels, the query load, the squared distance of a point to one primitive — a PrecomputedTri {p0, e1 = p0 - p1, e2 = p2 - p0, n}
+// What the per-lane bodies of the point, box and ray-list queries share (knn_body.inc; through nearest_walk.inc closest_body.inc and
+// ray_nearest_body.inc; through list_walk.inc radius_body.inc, overlap_body.inc and ray_hits_body.inc): the arguments common to their kernels, the query load, the squared distance of a point to one primitive — a PrecomputedTri {p0, e1 = p0 - p1, e2 = p2 - p0, n}
 // or a Sphere {c, r} — and to a box, the streaming stores of the outputs and the index arithmetic of the walk's three-tier stack. Kept as an
 // include so that the host harnesses (tests/cpp/*_body_host.cpp) compile the very same text, through the bodies, with one emulated lane
 // per query. Expects trace_device.h (Num, dot3, load_pair, load_prim12, load_prim4, kBlock) and common.h, or the harnesses' stand-ins
@@ -140,8 +140,8 @@ __device__ inline void store_stream(V* p, V v) {
 // the depth, conflict-free), the rest of the first kPointSmall in per-lane scratch, entries beyond (Deep kernels: trees deeper than
 // 64 levels only) in HBM, deep_cap per lane of the launch. A walk pushes at most one entry per level, so the tree's depth bounds the
 // stack; the indices are clamped all the same. These two give the index of entry sp in the scratch arrays of kPointSmall - Lds
-// entries (Lds <= sp) and in the HBM arrays (kPointSmall <= sp; `lane` of the launch). The accesses themselves stay in the bodies'
-// push / pop, on arrays they name: behind pointers held in a struct the compiler merges the LDS and scratch accesses of the
+// entries (Lds <= sp) and in the HBM arrays (kPointSmall <= sp; `lane` of the launch). The accesses themselves stay in the push / pop
+// of the two walks (list_walk.inc, nearest_walk.inc), of knn_body.inc and of instanced_body.inc, on arrays they name: behind pointers held in a struct the compiler merges the LDS and scratch accesses of the
 // non-Deep kernels into flat ones, at a cost in registers and occupancy (DESIGN.md, "Point queries: the shared launch path and walk kit").
 template <int Lds>
 __device__ inline uint32_t stack_small_at(uint32_t sp) {

@@ -2,7 +2,7 @@
 // the UNSHORTENED ray {org, dir, tmin, tmax} crosses, as a count and, optionally, a list of hit records in the ray's segment of a
 // caller-sized buffer. It is the third client of list_walk.inc, next to radius_body.inc and overlap_body.inc: the enter test is the
 // ray / box slab test of the ray walks (trace_device.h: ray_constants, slab_pair), the hit test their ray / primitive test
-// (tri_test.inc, the sphere expressions of trace_body.inc), both against the ray's own [tmin, tmax]: nothing a hit finds shortens
+// (ray_prim_test.inc: tri_test.inc, the sphere expressions of trace_body.inc; shared with ray_nearest_body.inc), both against the ray's own [tmin, tmax]: nothing a hit finds shortens
 // the ray, so the list is what the reference's intersect<false, Robust> reports to a leaf_fn that never shortens it.
 // Kept as an include so that tests/cpp/ray_hits_body_host.cpp compiles the very same text for the host (one emulated lane per ray).
 // Expects what point_walk.inc expects.
@@ -63,32 +63,11 @@ __device__ inline void ray_hits_lane(const RayHitsArgs<T>& a, unsigned long long
         },
         [&](uint32_t i, unsigned long long at, bool room) {
             if (Stats) ++cnt[1];
-            // (TWIN COPY of the two tests below: ray_nearest_test in ray_nearest_body.inc; a fix to one belongs in the other)
+            const T* const prims = a.prims;                                     // (the names ray_prim_test.inc expects)
             T tmax = ray_tmax;                                                  // this test's own copy: what it finds shortens nothing else
             T hit_t = T(0), hit_u = T(0), hit_v = T(0);
             bool accepted = false;
-            if (Leaf == LEAF_TRIANGLE) {                                        // tri.h:56-74
-                T p[12];
-                load_prim12(a.prims + 12ull * i, p);
-#define BVH_TRI_ACCEPTED accepted = true
-#include "tri_test.inc"
-#undef BVH_TRI_ACCEPTED
-            } else {                                                            // sphere.h:32-49, as trace_body.inc writes it
-                T s[4];
-                load_prim4(a.prims + 4ull * i, s);
-                const T o0 = org[0] - s[0], o1 = org[1] - s[1], o2 = org[2] - s[2];
-                const T qa = dot3(dir[0], dir[1], dir[2], dir[0], dir[1], dir[2]);
-                const T qb = T(2) * dot3(dir[0], dir[1], dir[2], o0, o1, o2);
-                const T qc = dot3(o0, o1, o2, o0, o1, o2) - s[3] * s[3];
-                const T delta = qb * qb - T(4) * qa * qc;
-                if (delta >= 0) {
-                    const T iv = -T(0.5) / qa;
-                    const T root = Num<T>::sqrt_(delta);
-                    const T t0 = pick_max((qb + root) * iv, tmin);
-                    const T t1 = pick_min((qb - root) * iv, tmax);
-                    if (t0 <= t1) { hit_t = t0; hit_u = t1; hit_v = T(0); accepted = true; }
-                }
-            }
+#include "ray_prim_test.inc"
             if (!accepted) return false;
             if (room) store_record(a.list_hits + at, a.prim_ids ? a.prim_ids[i] : i, hit_t, hit_u, hit_v);
             return true;

@@ -335,3 +335,23 @@ def test_deep_chain_fills_the_spill(dll, orc):
     assert (hits["prim"] == bi).all() and (hits["prim"] == depth).all()
     assert (hits["t"] == np.sqrt(brute_d2)).all()
     assert cnt[0] == depth * len(q)                          # every level's record fetched once: nothing popped was walked again
+
+
+def test_tie_across_leaves_entry_at_the_limit_is_kept(dll):
+    """Two triangles in two leaves, both at distance exactly 2 from the query. The right leaf's box reaches nearer (1) than its
+    triangle, so the walk goes right, stacks the left leaf with key 4 and finds primitive 1 at d2 = 4 = the stacked key. Primitive 0
+    wins the tie by its index, which only a pop that keeps an entry AT the limit (key <= best, not <) gets to see."""
+    from oracle import NODEF
+    tris = np.array([[-2, -1, -1, -2, 1, -1, -2, 0, 1], [2, -1, -1, 2, 1, -1, 2, 0, 1]], dtype=np.float32)
+    nodes = np.zeros(3, dtype=NODEF)
+    nodes[0]["bounds"], nodes[0]["index"] = [-2, 2, -1, 1, -1, 1], 1 << 4
+    nodes[1]["bounds"], nodes[1]["index"] = [-2, -2, -1, 1, -1, 1], (0 << 4) | 1
+    nodes[2]["bounds"], nodes[2]["index"] = [1, 2, -1, 1, -1, 1], (1 << 4) | 1
+    prims = precompute(tris, np.float32)
+    q = np.array([[0, 0, 0, np.inf]], dtype=np.float32)
+    d2, bi = host_brute(dll, prims, q, 0)
+    assert d2[0] == 4 and bi[0] == 0
+    assert (host_eval(dll, prims, np.repeat(q, 2, axis=0), [0, 1], 0) == 4).all()
+    hits, cnt = host_walk(dll, nodes["bounds"], nodes["index"], prims, q, 0)
+    assert hits["prim"][0] == 0 and hits["t"][0] == 2
+    assert list(cnt) == [1, 2, 2]                             # one record, both leaves, both triangles
