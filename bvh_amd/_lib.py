@@ -159,6 +159,8 @@ _SIGS_T = {
     "bvh{S}_intersect_rays_nearest_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P]),
     "bvh{S}_knn_tri": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_knn_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
+    "bvh{S}_winding_prepare": (_I, [_P, _P, _P, _Z, _P]),
+    "bvh{S}_winding_numbers": (_I, [_P, _P, _P, _Z, _P, _Z, C.c_double, _U, _P, _P, _P, _P]),
     "bvh{S}_overlap_boxes": (_I, [_P, _P, _Z, _P, _Z, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_overlap_self": (_I, [_P, _P, _Z, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_intersect_tris": (_I, [_P, _P, _Z, _P, _Z, _U, _P, _P, _P, _P, _P]),
@@ -208,6 +210,7 @@ _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_inter
             "bvh{S}_intersect_rays_all_tri", "bvh{S}_intersect_rays_all_sphere",                      # and the all-hits ray queries
             "bvh{S}_intersect_rays_nearest_tri", "bvh{S}_intersect_rays_nearest_sphere",              # and the nearest-hits ray queries
             "bvh{S}_knn_tri", "bvh{S}_knn_sphere",                                                    # and the k-nearest queries
+            "bvh{S}_winding_prepare", "bvh{S}_winding_numbers",                                       # and the winding numbers
             "bvh{S}_overlap_boxes", "bvh{S}_overlap_self",                                            # and the box-overlap queries
             "bvh{S}_intersect_tris", "bvh{S}_intersect_tris_self",                                    # and the triangle-intersection queries
             "bvh{S}_instance_prepare", "bvh{S}_intersect_rays_instanced",                             # and the instanced ray queries

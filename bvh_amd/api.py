@@ -568,6 +568,69 @@ def _sort_flags(sort_queries, original_ids=False):
     return (0 if sort_queries is None else RayFlags.SORTED if sort_queries else RayFlags.UNSORTED) | (8 if original_ids else 0)
 
 
+def winding_prepare(bvh: Bvh, prims, out=None):
+    """The per-node moments the winding-number queries read (bvh3X_winding_prepare): a (node_count + 1, 8) tensor of the tree's scalar
+    type, node c in row c + 1 as {cx, cy, cz, r2, Nx, Ny, Nz, area}, written into `out` if given. prims: the BVH-order (n, 12)
+    PrecomputedTri. The tree is only read. The moments are stale after Bvh.refit_tris and Bvh.optimize: prepare them again."""
+    torch = _torch()
+    if bvh.dim != 3:
+        raise TypeError("winding_prepare: 3D trees only")
+    dt = torch.float32 if bvh._s[1] == "f" else torch.float64
+    p = _dev(prims, 12)
+    if p.dtype != dt:
+        raise TypeError("prims dtype must match the BVH scalar type")
+    rows = bvh.node_count + 1
+    if out is None:
+        out = torch.empty((rows, 8), dtype=dt, device=p.device)
+    elif out.dtype != dt or not out.is_contiguous() or out.numel() < rows * 8:
+        raise TypeError("winding_prepare: out must be a contiguous (node_count + 1, 8) tensor of the BVH scalar type")
+    _lib.check(getattr(_lib.load(), f"bvh{bvh._s}_winding_prepare")(bvh._h, p.data_ptr(), out.data_ptr(), out.numel() // 8, _stream()), "winding_prepare")
+    return out
+
+
+def _winding_call(bvh: Bvh, p, moments, q, beta, sort_queries, counters: bool, out, hits, who: str):
+    torch = _torch()
+    m = _dev(moments)
+    if m.dtype != q.dtype:
+        raise TypeError("moments dtype must match the BVH scalar type")
+    n = q.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=q.dtype, device=q.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_winding_numbers")
+    _lib.check(fn(bvh._h, p.data_ptr(), m.data_ptr(), m.numel() // 8, q.data_ptr(), n, float(beta), int(_sort_flags(sort_queries)), out.data_ptr(),
+                  hits.data_ptr() if hits is not None else None, cnt.data_ptr() if counters else None, _stream()), who)
+    return out, cnt
+
+
+def winding_numbers(bvh: Bvh, prims, moments, points, beta: float = 2.0, sort_queries=None, counters: bool = False, out=None):
+    """For each point, the generalized winding number of the triangle mesh (bvh3X_winding_numbers): 1 inside and 0 outside a closed mesh
+    whose (p1 - p0) x (p2 - p0) point outward, 0 in the cavity of a shell, 2 inside a doubled surface, fractional near the holes of an
+    open or defective mesh. prims: the BVH-order (n, 12) PrecomputedTri; moments: winding_prepare's tensor for the same tree and
+    triangles. points: (n, 3), or (n, 4) as closest_points takes them (column 3 is not read). beta >= 1 trades speed for accuracy: a
+    node farther than beta radii is replaced by one dipole; inf gives the exact sum. Returns the (n,) tensor of the tree's scalar type
+    (NaN for a point with a NaN or infinite coordinate); with counters also (pair records opened, triangles summed, far terms added).
+    sort_queries: True / False force / forbid reordering the batch internally (None: the library decides); values never change."""
+    q, p, _ = _point_query_args(bvh, prims, points, 0.0, "tri", "winding_numbers", "max_distance", 0.0)
+    w, cnt = _winding_call(bvh, p, moments, q, beta, sort_queries, counters, out, None, "winding_numbers")
+    return (w, cnt) if counters else w
+
+
+def signed_distance(bvh: Bvh, prims, moments, points, beta: float = 2.0, max_distance: float = float("inf"), sort_queries=None, out=None):
+    """closest_points' (n, 4) hit records with a signed t: negative where the winding number is at least 1/2 (bvh3X_closest_points_tri,
+    then bvh3X_winding_numbers on the same queries with the records as d_hits). Every other field is closest_points'; a miss keeps
+    prim = INVALID and carries +-max_distance."""
+    q, p, dt = _point_query_args(bvh, prims, points, max_distance, "tri", "signed_distance", "max_distance", float("inf"))
+    hits = closest_points(bvh, p, q, sort_queries=sort_queries, out=out)
+    _winding_call(bvh, p, moments, q, beta, sort_queries, False, None, hits, "signed_distance")
+    return hits
+
+
+def occupancy(bvh: Bvh, prims, moments, points, beta: float = 2.0, sort_queries=None):
+    """For each point, whether it is inside the mesh: winding_numbers(...) >= 0.5 as an (n,) bool tensor (False for a NaN point)."""
+    return winding_numbers(bvh, prims, moments, points, beta=beta, sort_queries=sort_queries) >= 0.5
+
+
 def offsets_from_counts(counts):
     """(n + 1,) int64 offsets {0, c0, c0 + c1, ...} of an (n,) int32 tensor of counts, on the device and without a read-back
     (bvh_amd_offsets_from_counts)."""

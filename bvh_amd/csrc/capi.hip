@@ -559,6 +559,23 @@ int knn(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const
 }
 
 template <typename T>
+int winding_prepare(const typename Family<T, 3>::Bvh* bvh, const T* d_tris12, T* d_moments, size_t moments_rows, void* stream)
+{
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, 1, "winding_prepare", &b)) return rc;
+    return launch_winding_prepare<T>(*b, d_tris12, d_moments, moments_rows, static_cast<hipStream_t>(stream));
+}
+
+template <typename T>
+int winding_numbers(const typename Family<T, 3>::Bvh* bvh, const T* d_tris12, const T* d_moments, size_t moments_rows, const T* d_queries4, size_t n,
+                    double beta, unsigned flags, T* d_w, typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, void* stream)
+{
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, n, "winding_numbers", &b)) return rc;
+    return launch_winding<T>(*b, d_tris12, d_moments, moments_rows, d_queries4, n, beta, flags, d_w, d_hits, d_counters, static_cast<hipStream_t>(stream));
+}
+
+template <typename T>
 int ray_hits(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const typename Family<T, 3>::Ray* d_rays, size_t n, unsigned flags,
              uint32_t* d_counts, const uint64_t* d_offsets, typename HitOf<T>::Type* d_list_hits, bvh_amd_counters* d_counters, void* stream)
 {
@@ -848,6 +865,11 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_knn_sphere(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned k, unsigned flags, uint32_t* out_prims, \
                             T* out_dist, uint32_t* counts, bvh_amd_counters* cnt, void* s) {                        \
         return knn<T>(b, LEAF_SPHERE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }                \
+    int bvh##S##_winding_prepare(const bvh##S* b, const T* tris, T* moments, size_t moments_rows, void* s) {        \
+        return winding_prepare<T>(b, tris, moments, moments_rows, s); }                                             \
+    int bvh##S##_winding_numbers(const bvh##S* b, const T* tris, const T* moments, size_t moments_rows, const T* queries, size_t n, \
+                                 double beta, unsigned flags, T* w, bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) { \
+        return winding_numbers<T>(b, tris, moments, moments_rows, queries, n, beta, flags, w, hits, cnt, s); }       \
     int bvh##S##_overlap_boxes(const bvh##S* b, const T* bboxes, size_t n_boxes, const T* queries6, size_t n, unsigned flags, uint32_t* counts, \
                                const uint64_t* offsets, uint32_t* list_prims, bvh_amd_counters* cnt, void* s) {          \
         return overlap<T>(b, false, bboxes, n_boxes, queries6, n, flags, counts, offsets, list_prims, cnt, s); }        \

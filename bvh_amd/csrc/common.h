@@ -311,6 +311,14 @@ int launch_instanced(const BvhImpl<T>& top, const GeomRef<T>* geoms, size_t n_ge
 template <typename T>
 int launch_knn(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T* d_queries, size_t n, unsigned k, unsigned flags, uint32_t* d_out_prims,
                T* d_out_dist, uint32_t* d_counts, bvh_amd_counters* d_counters, hipStream_t stream);
+// winding.hip: the per-node moments of a triangle tree into the caller's (node_count + 1) x 8 scalars (reads the tree only), and batched
+// winding numbers, n x {x, y, z, -} -> one scalar each; with d_hits, closest_points' records of the same queries get t negated where
+// w >= 1/2 (flags: SORTED, UNSORTED)
+template <typename T>
+int launch_winding_prepare(const BvhImpl<T>& b, const T* d_tris12, T* d_moments, size_t moments_rows, hipStream_t stream);
+template <typename T>
+int launch_winding(const BvhImpl<T>& b, const T* d_tris12, const T* d_moments, size_t moments_rows, const T* d_queries, size_t n, double beta,
+                   unsigned flags, T* d_w, typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, hipStream_t stream);
 void last_launch_plan(int out[4]);                            // traverse.hip: {reordered, coop, refill, leaf} of the calling thread's latest launch
 int wave_times(unsigned long long* out, size_t capacity_waves, size_t* n_waves);   // traverse.hip: developer library only
 void last_plan_search(float ns_per_ray[5], int measurements[5], unsigned* dropped);   // traverse.hip

@@ -6,6 +6,7 @@
 // synchronisation, no allocation beyond two words per node from the per-stream scratch cache. The text of the fold, the record-half
 // store and the climb is refit_body.inc, which a CPU test compiles for the host.
 #include "build_common.h"
+#include "climb_parents.h"
 
 namespace bvh_amd {
 
@@ -35,17 +36,12 @@ namespace bvh_amd {
 namespace {
 
 // compute_parents (reinsertion_optimizer.h:72-86) over a parent[] pre-filled with 0xFFFFFFFF: the root and the top of a subtree
-// nothing references keep that mark
+// nothing references keep that mark (climb_parents.h: shared with the moments climb of winding.hip)
 template <typename T>
 __global__ void __launch_bounds__(256) k_refit_parents(const HostNode<T>* nodes, uint32_t n, uint32_t* parent) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const auto index = nodes[i].index;
-    if ((index & kCountMask) != 0) return;
-    const size_t f = static_cast<size_t>(index >> kCountBits);
-    if (f == 0 || f + 1 >= n) return;                         // (never in a validated tree)
-    parent[f] = i;
-    parent[f + 1] = i;
+    climb_note_parent(nodes[i].index, i, n, parent);
 }
 
 template <typename T, int Src>

@@ -326,6 +326,8 @@ template <> struct Api<float, 3> {
     static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3f_intersect_rays_nearest_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, k, f, static_cast<bvh_hit3f*>(hits), counts, nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
+    static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh3f_winding_prepare(h, static_cast<const float*>(tris), static_cast<float*>(moments), rows, nullptr); }
+    static int winding_numbers(const Handle* h, const void* tris, const void* moments, size_t rows, const void* queries, size_t n, double beta, unsigned f, void* w, void* hits) { return bvh3f_winding_numbers(h, static_cast<const float*>(tris), static_cast<const float*>(moments), rows, static_cast<const float*>(queries), n, beta, f, static_cast<float*>(w), static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_boxes(h, static_cast<const float*>(bb), nb, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_self(h, static_cast<const float*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
     static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_intersect_tris(h, static_cast<const float*>(t9), nt, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
@@ -375,6 +377,8 @@ template <> struct Api<double, 3> {
     static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3d_intersect_rays_nearest_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, k, f, static_cast<bvh_hit3d*>(hits), counts, nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
+    static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh3d_winding_prepare(h, static_cast<const double*>(tris), static_cast<double*>(moments), rows, nullptr); }
+    static int winding_numbers(const Handle* h, const void* tris, const void* moments, size_t rows, const void* queries, size_t n, double beta, unsigned f, void* w, void* hits) { return bvh3d_winding_numbers(h, static_cast<const double*>(tris), static_cast<const double*>(moments), rows, static_cast<const double*>(queries), n, beta, f, static_cast<double*>(w), static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_boxes(h, static_cast<const double*>(bb), nb, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_self(h, static_cast<const double*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
     static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_intersect_tris(h, static_cast<const double*>(t9), nt, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
@@ -924,6 +928,37 @@ void closest_points_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typenam
     DeviceArray<Hit<T>> d_hits(queries.size());
     closest_points_batch(bvh, spheres, d_queries, d_hits);
     d_hits.download(hits);
+}
+
+// Winding numbers (include/bvh_amd.h: bvh3X_winding_prepare / bvh3X_winding_numbers): is a point inside the mesh? winding_prepare
+// fills `moments` with the tree's node_count + 1 rows of 8 scalars (stale after refit_tris and optimize: prepare again);
+// winding_numbers_batch writes one winding number per query (1 inside a closed mesh whose (p1 - p0) x (p2 - p0) point outward, 0
+// outside; the queries' max_distance is not read; beta >= 1, +inf = the exact sum); signed_distance_batch is closest_points_batch
+// followed by the walk over its records: hit.t is negated where the winding number is at least 1/2.
+template <typename Node>
+void winding_prepare(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, DeviceArray<typename Node::Scalar>& moments) {
+    using T = typename Node::Scalar;
+    check(Api<T, 3>::winding_prepare(bvh.device(), prims.data(), moments.data(), moments.size() / 8), "winding_prepare");
+}
+template <typename Node>
+void winding_numbers_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims,
+                           const DeviceArray<typename Node::Scalar>& moments, const DeviceArray<PointQuery<typename Node::Scalar>>& queries,
+                           DeviceArray<typename Node::Scalar>& w, double beta = 2.0) {
+    using T = typename Node::Scalar;
+    if (w.size() < queries.size()) throw Error("winding_numbers_batch: one output per query");
+    check(Api<T, 3>::winding_numbers(bvh.device(), prims.data(), moments.data(), moments.size() / 8, queries.data(), queries.size(), beta, 0u, w.data(), nullptr),
+          "winding_numbers");
+}
+template <typename Node>
+void signed_distance_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims,
+                           const DeviceArray<typename Node::Scalar>& moments, const DeviceArray<PointQuery<typename Node::Scalar>>& queries,
+                           DeviceArray<Hit<typename Node::Scalar>>& hits, double beta = 2.0) {
+    using T = typename Node::Scalar;
+    if (hits.size() < queries.size()) throw Error("signed_distance_batch: one record per query");
+    closest_points_batch(bvh, prims, queries, hits);
+    DeviceArray<T> w(queries.size());
+    check(Api<T, 3>::winding_numbers(bvh.device(), prims.data(), moments.data(), moments.size() / 8, queries.data(), queries.size(), beta, 0u, w.data(), hits.data()),
+          "winding_numbers");
 }
 
 // For each query, every primitive within its max_distance (include/bvh_amd.h: bvhXX_radius_search_*), in the order the tree fixes.

@@ -579,6 +579,51 @@ BVH_AMD_API int bvh3f_knn_sphere(const struct bvh3f*, const float* d_sph4, const
 BVH_AMD_API int bvh3d_knn_sphere(const struct bvh3d*, const double* d_sph4, const double* d_queries4, size_t n, unsigned k, unsigned flags,
     uint32_t* d_out_prims, double* d_out_dist, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
 
+/* ---- batched winding numbers: is a point inside the mesh? (and, with closest_points, signed distance) ------------------------------ */
+/* The generalized winding number of the triangle mesh at each query point, evaluated hierarchically (Barill et al., "Fast Winding
+ * Numbers for Soups and Clouds", 2018; first order): for a closed mesh whose ab x ac = (p1 - p0) x (p2 - p0) point outward it is 1
+ * inside and 0 outside; it is 0 in the cavity of a shell (an inner surface facing the cavity), 2 inside a doubled surface, and degrades
+ * to fractional values near the holes of an open or defective mesh instead of flipping as crossing parity does. (d_tris12 holds
+ * n = cross(p0 - p1, p2 - p0) = -(ab x ac); the area vector of a triangle is A = (ab x ac) / 2 = -n / 2.)
+ *
+ * bvh3X_winding_prepare writes the per-node moments into the CALLER's buffer d_moments: moments_rows >= node_count + 1 rows of 8
+ * scalars of the tree's type (32 B / 64 B a row). Node c is row c + 1, row 0 is zero, so the two children of a pair record share one
+ * aligned 16-scalar line. A row is {cx, cy, cz, r2, Nx, Ny, Nz, area}: N = the sum of the area vectors below the node, area = the sum
+ * of their lengths, c = the area-weighted mean of the triangles' centroids (the centre of the node's box when area is 0), r2 = the
+ * squared distance from c to the farthest corner of the node's box. A leaf sums its triangles in ascending BVH-order index, an inner
+ * node is always left + right: the bytes depend on the tree and the triangles only. r2 bounds the triangles as long as the tree's
+ * boxes do (after a build or bvh3X_refit_tris). Asynchronous on `stream`; reads the tree (its traversal records) and writes only
+ * d_moments: re-entrant on a const tree. The moments are STALE after bvh3X_refit_tris and after bvhXX_optimize: prepare them again.
+ *
+ * bvh3X_winding_numbers: d_queries4 is the array bvhXX_closest_points_* take, n x {x, y, z, ignored} (the max_distance slot is not
+ * read). Per query, depth-first from the root, the left child before the right, nothing pruned against what was found: a node with
+ * |c - q|^2 > beta^2 r2 adds N . (c - q) / |c - q|^3; otherwise a leaf adds, for each of its triangles in ascending index, the solid
+ * angle 2 atan2(det(a, b, c), |a||b||c| + (a.b)|c| + (a.c)|b| + (b.c)|a|) (a, b, c = the vertices minus q; a zero determinant adds 0),
+ * and an inner node is opened. d_w[q] = sum / 4 pi, accumulated in the tree's type in that order.
+ *   beta:    the accuracy knob, >= 1; 2 is the default of the other layers, +inf never takes the far branch and gives the exact sum.
+ *            beta < 1 or NaN: BVH_AMD_ERR_ARG.
+ *   special: a NaN or infinite query coordinate gives w = NaN and leaves the query's hit record alone. Finite input never yields NaN or inf as long as
+ *            the product of three distances from a query to the mesh is representable: with d the largest such distance, 8 d^3 must
+ *            not overflow (float: d below about 3e12; double: 8e101) and d^2 must not underflow. ON the surface the value lies between the two sides' values and is
+ *            otherwise unspecified.
+ *   d_hits:  optional, the records bvh3X_closest_points_tri wrote for the same queries: t is negated where w >= 1/2, nothing else is
+ *            touched. That is the whole of signed distance (negative inside).
+ *   flags:   BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED as for closest_points (with neither, batches of >= 1M queries are reordered
+ *            internally). BVH_AMD_RAY_ORIGINAL_IDS is refused (there is nothing to map), like any other bit. n == 0 is a no-op.
+ * A value depends only on the tree, the triangles, the moments, beta and its query: not on batch size, position or order, the flags,
+ * the stream or the thread. d_counters (optional) receives {pair records opened, triangles summed exactly, far terms added}.
+ * Alignment: d_tris12, d_moments, d_queries4 and d_hits 16 bytes, d_counters 8, d_w its element. 3D trees only; a 2D tree, a NULL
+ * handle, NULL tris, moments, queries or d_w, a misaligned pointer, moments_rows < node_count + 1 and a tree without a device copy
+ * are refused with BVH_AMD_ERR_ARG and nothing is written. Re-entrant on a const tree (no work slot of the tree is claimed). */
+BVH_AMD_API int bvh3f_winding_prepare(const struct bvh3f*, const float* d_tris12, float* d_moments, size_t moments_rows, void* stream);
+BVH_AMD_API int bvh3d_winding_prepare(const struct bvh3d*, const double* d_tris12, double* d_moments, size_t moments_rows, void* stream);
+BVH_AMD_API int bvh3f_winding_numbers(const struct bvh3f*, const float* d_tris12, const float* d_moments, size_t moments_rows,
+    const float* d_queries4, size_t n, double beta, unsigned flags, float* d_w, struct bvh_hit3f* d_hits, struct bvh_amd_counters* d_counters,
+    void* stream);
+BVH_AMD_API int bvh3d_winding_numbers(const struct bvh3d*, const double* d_tris12, const double* d_moments, size_t moments_rows,
+    const double* d_queries4, size_t n, double beta, unsigned flags, double* d_w, struct bvh_hit3d* d_hits, struct bvh_amd_counters* d_counters,
+    void* stream);
+
 /* ---- batched box-overlap queries and self-overlap pairs (broad phase) ------------------------------------------------------------ */
 /* d_bboxes is the array bvhXX_build_device and bvhXX_refit_boxes take: n_boxes x {min.xyz, max.xyz}, indexed by ORIGINAL primitive
  * id; the box of BVH-order primitive i is d_bboxes[prim_ids[i]], so the kind of primitive the tree was built over does not matter.
