@@ -48,6 +48,7 @@ class BBox2d(C.Structure):
 
 # name -> (restype, argtypes); `{S}` expands to 3f / 3d
 _P, _Z, _I, _U = C.c_void_p, C.c_size_t, C.c_int, C.c_uint
+_T = object()                                 # in _SIGS_T: a scalar of the family's type passed by value (c_float / c_double)
 _SIGS = {
     "bvh_amd_last_error": (C.c_char_p, []),
     "bvh_amd_version": (C.c_char_p, []),
@@ -157,6 +158,8 @@ _SIGS_T = {
     "bvh{S}_intersect_rays_all_sphere": (_I, [_P, _P, _P, _Z, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_intersect_rays_nearest_tri": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P]),
     "bvh{S}_intersect_rays_nearest_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P]),
+    "bvh{S}_sphere_cast_tri": (_I, [_P, _P, _P, _Z, _T, _P, _U, _P, _P, _P]),                 # (_T: the family's scalar, by value)
+    "bvh{S}_sphere_cast_sphere": (_I, [_P, _P, _P, _Z, _T, _P, _U, _P, _P, _P]),
     "bvh{S}_knn_tri": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_knn_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_winding_prepare": (_I, [_P, _P, _P, _Z, _P]),
@@ -209,6 +212,7 @@ _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_inter
             "bvh{S}_radius_search_tri", "bvh{S}_radius_search_sphere",                                # and the radius queries
             "bvh{S}_intersect_rays_all_tri", "bvh{S}_intersect_rays_all_sphere",                      # and the all-hits ray queries
             "bvh{S}_intersect_rays_nearest_tri", "bvh{S}_intersect_rays_nearest_sphere",              # and the nearest-hits ray queries
+            "bvh{S}_sphere_cast_tri", "bvh{S}_sphere_cast_sphere",                                    # and the sphere-cast queries
             "bvh{S}_knn_tri", "bvh{S}_knn_sphere",                                                    # and the k-nearest queries
             "bvh{S}_winding_prepare", "bvh{S}_winding_numbers",                                       # and the winding numbers
             "bvh{S}_overlap_boxes", "bvh{S}_overlap_self",                                            # and the box-overlap queries
@@ -245,7 +249,7 @@ def load():
             if s[0] == "2" and name in _ONLY_3D:
                 continue
             f = getattr(lib, name.format(S=s))
-            f.restype, f.argtypes = res, args
+            f.restype, f.argtypes = res, [(C.c_float if s[1] == "f" else C.c_double) if a is _T else a for a in args]
     lib.bvh_node3f_get_bbox.restype, lib.bvh_node3f_get_bbox.argtypes = BBox3f, [_P]
     lib.bvh_node3d_get_bbox.restype, lib.bvh_node3d_get_bbox.argtypes = BBox3d, [_P]
     lib.bvh_node2f_get_bbox.restype, lib.bvh_node2f_get_bbox.argtypes = BBox2f, [_P]

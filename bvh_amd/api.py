@@ -788,6 +788,43 @@ def ray_hits_nearest(bvh: Bvh, prims, rays, k: int, leaf: str = "tri", robust: b
     return (hits, counts, cnt) if counters else (hits, counts)
 
 
+def sphere_cast(bvh: Bvh, prims, rays, radius, leaf: str = "tri", robust: bool = False, original_ids: bool = False, sort_queries=None,
+                counters: bool = False, out=None):
+    """For each ray {org, dir, tmin, tmax}, the first contact of a ball of the given radius whose centre moves along org + t dir
+    (bvh3X_sphere_cast_*): the smallest t in [tmin, tmax] at which the ball touches a solid triangle or solid sphere, ties to the
+    lowest BVH-order index among the primitives the walk tests. radius: a float for the whole batch, or an array / tensor of n.
+    prims are in BVH order, as for closest_points. Returns the (n, 4) tensor of hit records (hits_to_numpy views it), written into
+    `out` if given: prim = BVH-order index (bvh.prim_ids[i] with original_ids) or INVALID, t = the contact's ray parameter (t == tmin:
+    the ball overlaps at its start; tmax on a miss), (u, v) = the barycentrics of the contact point on a triangle in closest_points'
+    convention (0 for spheres): the contact normal is (org + t dir - point) / radius. A NaN or negative radius, a NaN tmin or tmax:
+    a miss. robust=True takes the robust box test: wanted for axis-parallel sweeps (a direction component of exactly 0), which the
+    fast test loses as intersect's does. With counters also (pairs, tests, leaves). sort_queries: True / False force / forbid reordering the batch internally
+    (None: the library decides); records never change."""
+    torch = _torch()
+    r, p, dt = _ray_query_args(bvh, prims, rays, leaf, "sphere_cast")
+    n = r.shape[0]
+    radii = None
+    if isinstance(radius, (int, float)):
+        scalar = float(radius)
+    else:
+        scalar = 0.0
+        radii = _dev(radius)
+        if radii.dtype != dt:
+            raise TypeError("radius dtype must match the BVH scalar type")
+        if radii.dim() != 1 or radii.shape[0] != n:
+            raise ValueError(f"sphere_cast: radius must be a float or hold one radius per ray ({n}), got shape {tuple(radii.shape)}")
+    if out is None:
+        out = torch.empty((n, 4), dtype=dt, device=r.device)
+    elif out.dtype != dt or not out.is_contiguous() or out.numel() < n * 4:
+        raise TypeError("sphere_cast: out must be a contiguous (n, 4) tensor of the BVH scalar type")
+    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_sphere_cast_{leaf}")
+    flags = int(_sort_flags(sort_queries, original_ids)) | (int(RayFlags.ROBUST) if robust else 0)
+    _lib.check(fn(bvh._h, p.data_ptr(), r.data_ptr(), n, scalar, radii.data_ptr() if radii is not None and n else None, flags, out.data_ptr(),
+                  cnt.data_ptr() if counters else None, _stream()), "sphere_cast")
+    return (out, cnt) if counters else out
+
+
 def _overlap_args(bvh: Bvh, bboxes, query_boxes, who: str):
     """The checks of the box-overlap queries: ((n_boxes, 6) boxes by original id, (n, 6) query boxes or None)."""
     if bvh.dim != 3:

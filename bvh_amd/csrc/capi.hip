@@ -595,6 +595,16 @@ int ray_nearest(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prim
                                  static_cast<hipStream_t>(stream));
 }
 
+template <typename T>
+int sphere_cast(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, const typename Family<T, 3>::Ray* d_rays, size_t n, T radius,
+                const T* d_radii, unsigned flags, typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, void* stream)
+{
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, n, "sphere_cast", &b)) return rc;
+    return launch_sphere_cast<T>(*b, leaf, d_prims, reinterpret_cast<const T*>(d_rays), n, radius, d_radii, flags, d_hits, d_counters,
+                                 static_cast<hipStream_t>(stream));
+}
+
 // bvh3X_overlap_boxes / bvh3X_overlap_self: d_queries6 = NULL and n = the tree's primitive count in self mode.
 template <typename T>
 int overlap(const typename Family<T, 3>::Bvh* bvh, bool self, const T* d_bboxes, size_t n_boxes, const T* d_queries6, size_t n, unsigned flags,
@@ -859,6 +869,12 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_intersect_rays_nearest_sphere(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, unsigned k, unsigned flags, \
                                                bvh_hit##S* out_hits, uint32_t* counts, bvh_amd_counters* cnt, void* s) {    \
         return ray_nearest<T>(b, LEAF_SPHERE, prims, rays, n, k, flags, out_hits, counts, cnt, s); }                \
+    int bvh##S##_sphere_cast_tri(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, T radius, const T* radii, unsigned flags, \
+                                 bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                                \
+        return sphere_cast<T>(b, LEAF_TRIANGLE, prims, rays, n, radius, radii, flags, hits, cnt, s); }              \
+    int bvh##S##_sphere_cast_sphere(const bvh##S* b, const T* prims, const bvh_ray##S* rays, size_t n, T radius, const T* radii, unsigned flags, \
+                                    bvh_hit##S* hits, bvh_amd_counters* cnt, void* s) {                             \
+        return sphere_cast<T>(b, LEAF_SPHERE, prims, rays, n, radius, radii, flags, hits, cnt, s); }                \
     int bvh##S##_knn_tri(const bvh##S* b, const T* prims, const T* queries, size_t n, unsigned k, unsigned flags, uint32_t* out_prims, \
                          T* out_dist, uint32_t* counts, bvh_amd_counters* cnt, void* s) {                           \
         return knn<T>(b, LEAF_TRIANGLE, prims, queries, n, k, flags, out_prims, out_dist, counts, cnt, s); }        \

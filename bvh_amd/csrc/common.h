@@ -294,6 +294,11 @@ int launch_ray_hits(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const 
 template <typename T>
 int launch_ray_nearest(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T* d_rays, size_t n, unsigned k, unsigned flags,
                        typename HitOf<T>::Type* d_out_hits, uint32_t* d_counts, bvh_amd_counters* d_counters, hipStream_t stream);
+// sphere_cast.hip: batched sphere-cast queries, n x {org, dir, tmin, tmax} and a radius (d_radii[n], or `radius` for all) -> per query
+// the hit record of the first contact of the swept ball (flags: ROBUST, ORIGINAL_IDS, SORTED, UNSORTED)
+template <typename T>
+int launch_sphere_cast(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, const T* d_rays, size_t n, T radius, const T* d_radii, unsigned flags,
+                       typename HitOf<T>::Type* d_hits, bvh_amd_counters* d_counters, hipStream_t stream);
 // instanced.hip: two-level scenes. A geometry = {tree, its BVH-order PrecomputedTri} (the layout of struct bvh_amd_geometry3f / 3d).
 // launch_instance_prepare: n_instances x object-to-world 3 x 4 -> world-to-object 3 x 4 (NaN: disabled), world boxes {min, max},
 // centres. launch_instanced: n_rays through `top` (built over those boxes, prim ids = instance indices) and the instances' geometries ->

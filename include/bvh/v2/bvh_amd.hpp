@@ -324,6 +324,8 @@ template <> struct Api<float, 3> {
     static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3f_intersect_rays_all_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, counts, offsets, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int nearest_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3f_intersect_rays_nearest_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, k, f, static_cast<bvh_hit3f*>(hits), counts, nullptr, nullptr); }
     static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3f_intersect_rays_nearest_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, k, f, static_cast<bvh_hit3f*>(hits), counts, nullptr, nullptr); }
+    static int sphere_cast_tri(const Handle* h, const void* prims, const void* rays, size_t n, float radius, const float* radii, unsigned f, void* hits) { return bvh3f_sphere_cast_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, radius, radii, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
+    static int sphere_cast_sphere(const Handle* h, const void* prims, const void* rays, size_t n, float radius, const float* radii, unsigned f, void* hits) { return bvh3f_sphere_cast_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, radius, radii, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh3f_winding_prepare(h, static_cast<const float*>(tris), static_cast<float*>(moments), rows, nullptr); }
@@ -375,6 +377,8 @@ template <> struct Api<double, 3> {
     static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3d_intersect_rays_all_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, counts, offsets, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int nearest_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3d_intersect_rays_nearest_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, k, f, static_cast<bvh_hit3d*>(hits), counts, nullptr, nullptr); }
     static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3d_intersect_rays_nearest_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, k, f, static_cast<bvh_hit3d*>(hits), counts, nullptr, nullptr); }
+    static int sphere_cast_tri(const Handle* h, const void* prims, const void* rays, size_t n, double radius, const double* radii, unsigned f, void* hits) { return bvh3d_sphere_cast_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, radius, radii, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
+    static int sphere_cast_sphere(const Handle* h, const void* prims, const void* rays, size_t n, double radius, const double* radii, unsigned f, void* hits) { return bvh3d_sphere_cast_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, radius, radii, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh3d_winding_prepare(h, static_cast<const double*>(tris), static_cast<double*>(moments), rows, nullptr); }
@@ -1273,6 +1277,65 @@ void intersect_nearest_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<type
     using T = typename Node::Scalar;
     static_assert(Node::dimension == 3, "nearest-hits ray queries: 3D trees only");
     detail::nearest_hits_host<T>(&Api<T, 3>::nearest_hits_sphere, bvh.device(), spheres.data(), rays, k, detail::all_hits_flags<IsRobust>(flags), hits, counts, "intersect_rays_nearest_sphere");
+}
+
+// For each ray, the first contact of a ball whose centre moves along org + t dir, t in [tmin, tmax] (include/bvh_amd.h:
+// bvh3X_sphere_cast_*): one record {prim, t, u, v} per ray, the smallest t at which the ball touches a solid triangle or a solid
+// sphere (t == tmin: it overlaps at its start), (u, v) the barycentrics of the contact point in closest_points_batch's convention, or
+// intersect_batch's miss record. `radius` holds one radius for the whole batch or one per ray (a NaN or negative radius: a miss).
+// `flags`: BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED.
+namespace detail {
+template <typename T>
+using SphereCastFn = int (*)(const typename Api<T, 3>::Handle*, const void*, const void*, size_t, T, const T*, unsigned, void*);
+template <typename T>
+void sphere_cast_device(SphereCastFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, const DeviceArray<Ray<T, 3>>& rays, T radius,
+                        const DeviceArray<T>* radii, unsigned flags, DeviceArray<Hit<T>>& hits, const char* what) {
+    const size_t n = rays.size();
+    if (hits.size() < n || (radii && radii->size() != n)) throw Error(std::string(what) + ": hits need n records, radii exactly n scalars");
+    check(fn(h, prims, rays.data(), n, radius, radii ? radii->data() : nullptr, flags, hits.data()), what);
+}
+template <typename T>
+void sphere_cast_host(SphereCastFn<T> fn, const typename Api<T, 3>::Handle* h, const void* prims, std::span<const Ray<T, 3>> rays, std::span<const T> radius,
+                      unsigned flags, std::vector<Hit<T>>& hits, const char* what) {
+    const size_t n = rays.size();
+    if (radius.size() != 1 && radius.size() != n) throw Error(std::string(what) + ": radius holds one scalar or one per ray");
+    hits.resize(n);
+    if (n == 0) return;
+    DeviceArray<Ray<T, 3>> d_rays(rays);
+    DeviceArray<Hit<T>> d_hits(n);
+    if (radius.size() == 1) { sphere_cast_device<T>(fn, h, prims, d_rays, radius[0], nullptr, flags, d_hits, what); }
+    else { DeviceArray<T> d_radii(radius); sphere_cast_device<T>(fn, h, prims, d_rays, T(0), &d_radii, flags, d_hits, what); }
+    d_hits.download(std::span<Hit<T>>(hits));
+}
+} // namespace detail
+
+template <bool IsRobust, typename Node>
+void sphere_cast_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, const DeviceArray<Ray<typename Node::Scalar, 3>>& rays,
+                       typename Node::Scalar radius, const DeviceArray<typename Node::Scalar>* radii, DeviceArray<Hit<typename Node::Scalar>>& hits, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "sphere-cast queries: 3D trees only");
+    detail::sphere_cast_device<T>(&Api<T, 3>::sphere_cast_tri, bvh.device(), prims.data(), rays, radius, radii, detail::all_hits_flags<IsRobust>(flags), hits, "sphere_cast_tri");
+}
+template <bool IsRobust, typename Node>
+void sphere_cast_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, const DeviceArray<Ray<typename Node::Scalar, 3>>& rays,
+                       typename Node::Scalar radius, const DeviceArray<typename Node::Scalar>* radii, DeviceArray<Hit<typename Node::Scalar>>& hits, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "sphere-cast queries: 3D trees only");
+    detail::sphere_cast_device<T>(&Api<T, 3>::sphere_cast_sphere, bvh.device(), spheres.data(), rays, radius, radii, detail::all_hits_flags<IsRobust>(flags), hits, "sphere_cast_sphere");
+}
+template <bool IsRobust, typename Node>
+void sphere_cast_batch(const Bvh<Node>& bvh, const DeviceArray<PrecomputedTri<typename Node::Scalar>>& prims, std::span<const Ray<typename Node::Scalar, 3>> rays,
+                       std::span<const typename Node::Scalar> radius, std::vector<Hit<typename Node::Scalar>>& hits, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "sphere-cast queries: 3D trees only");
+    detail::sphere_cast_host<T>(&Api<T, 3>::sphere_cast_tri, bvh.device(), prims.data(), rays, radius, detail::all_hits_flags<IsRobust>(flags), hits, "sphere_cast_tri");
+}
+template <bool IsRobust, typename Node>
+void sphere_cast_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, std::span<const Ray<typename Node::Scalar, 3>> rays,
+                       std::span<const typename Node::Scalar> radius, std::vector<Hit<typename Node::Scalar>>& hits, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "sphere-cast queries: 3D trees only");
+    detail::sphere_cast_host<T>(&Api<T, 3>::sphere_cast_sphere, bvh.device(), spheres.data(), rays, radius, detail::all_hits_flags<IsRobust>(flags), hits, "sphere_cast_sphere");
 }
 
 // Two-level scenes (include/bvh_amd.h: bvh3X_instance_prepare / bvh3X_intersect_rays_instanced): a table of geometries {tree, its

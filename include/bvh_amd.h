@@ -798,6 +798,41 @@ BVH_AMD_API int bvh3f_intersect_rays_nearest_sphere(const struct bvh3f*, const f
 BVH_AMD_API int bvh3d_intersect_rays_nearest_sphere(const struct bvh3d*, const double* d_sph4, const struct bvh_ray3d* d_rays, size_t n, unsigned k,
     unsigned flags, struct bvh_hit3d* d_out_hits, uint32_t* d_counts, struct bvh_amd_counters* d_counters, void* stream);
 
+/* ---- batched sphere-cast queries: the first contact of a ball swept along a segment --------------------------------------------- */
+/* A query is a ray record {org, dir, tmin, tmax} and a radius r: d_radii[q] (n scalars, caller order) or, with d_radii == NULL,
+ * `radius` for the whole batch. The ball's centre is c(t) = org + t * dir for t in [tmin, tmax]; dir need not be unit length, t is the
+ * ray parameter and distances are Euclidean. A primitive is a SOLID triangle (BVH-order PrecomputedTri, 12 scalars) or a solid sphere
+ * (4 scalars), as bvh3X_closest_points_* takes them.
+ *   answer:  the smallest t in [tmin, tmax] with dist(c(t), primitive) <= r (closed), as one record {prim, t, u, v} per query.
+ *            (u, v) are the barycentrics of the contact point on the triangle in the convention of bvh3X_closest_points_*:
+ *            point = p0 - u * e1 + v * e2; the contact normal is (c(t) - point) / r. A sphere leaf writes u = v = 0.
+ *   overlap: a ball that already touches a primitive at tmin reports t = tmin (an initial overlap: t == tmin tells).
+ *   dir = 0: allowed; an overlap test at c(tmin). r = 0: allowed; a ray cast against the closed triangle in THIS function's
+ *            arithmetic (not promised to match the bits of bvh3X_intersect_rays_*).
+ *   miss:    {BVH_AMD_INVALID, the ray's tmax bits, 0, 0}: no contact, a NaN tmin or tmax, a NaN or negative radius.
+ *   ties:    among the primitives the walk tests, equal t go to the lowest BVH-order index (also under BVH_AMD_RAY_ORIGINAL_IDS,
+ *            which maps the reported prim only). The walk enters a child iff the ray meets its box grown by r on every side within
+ *            [tmin, best t so far], nearer entry first; a subtree whose grown box is computed to start behind the best t is skipped,
+ *            so, as for bvh3X_closest_points_*, the record is the brute force's argmin by (t, index) exactly when the arithmetic is
+ *            exact, otherwise within the residual stated in INTEGRATION.md 3l.
+ *   flags:   BVH_AMD_RAY_ROBUST (the robust box test), BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED (the
+ *            reordering key of the all-hits query; with neither, batches of >= 1M queries are reordered). Any other bit:
+ *            BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * A query's record depends only on the tree, the primitives, the ray, its radius and ROBUST / ORIGINAL_IDS: not on batch size,
+ * position or order, the reordering flags, the stream or the thread. d_counters (optional) receives {pair records fetched, primitives
+ * tested, leaves visited}. Alignment: d_prims and d_rays 16 bytes, d_hits to the size of its record (16 / 32), d_counters 8, d_radii
+ * to its scalar (4 / 8). 3D trees only; a 2D tree, a NULL handle, a NULL d_prims, d_rays or d_hits, a misaligned pointer and a tree
+ * without a device copy are refused with BVH_AMD_ERR_ARG. Re-entrant on a const tree (no work slot of the tree is claimed).
+ * Not offered: the 2D families, instanced scenes, swept capsules or boxes, a top-k variant. */
+BVH_AMD_API int bvh3f_sphere_cast_tri(const struct bvh3f*, const float* d_tris12, const struct bvh_ray3f* d_rays, size_t n, float radius,
+    const float* d_radii, unsigned flags, struct bvh_hit3f* d_hits, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_sphere_cast_tri(const struct bvh3d*, const double* d_tris12, const struct bvh_ray3d* d_rays, size_t n, double radius,
+    const double* d_radii, unsigned flags, struct bvh_hit3d* d_hits, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_sphere_cast_sphere(const struct bvh3f*, const float* d_sph4, const struct bvh_ray3f* d_rays, size_t n, float radius,
+    const float* d_radii, unsigned flags, struct bvh_hit3f* d_hits, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_sphere_cast_sphere(const struct bvh3d*, const double* d_sph4, const struct bvh_ray3d* d_rays, size_t n, double radius,
+    const double* d_radii, unsigned flags, struct bvh_hit3d* d_hits, struct bvh_amd_counters* d_counters, void* stream);
+
 /* ---- batched instanced ray queries: a two-level scene with transforms ---------------------------------------------------------- */
 /* A scene is a table of geometries {tree, its BVH-order PrecomputedTri, as bvh3X_intersect_rays_tri takes them}, n_instances
  * instances {object-to-world matrix, geometry index}, and a top tree: an ordinary bvh3X built over the instances' world boxes,
