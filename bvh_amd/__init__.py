@@ -10,6 +10,7 @@ Host-side mirror of the reference's interface for the hot path (names follow bvh
     ray_hits_nearest(bvh, prims, rays, k, leaf="tri", robust=False) -> hits, counts (the first k crossings of a ray, front to back, 3D)
     closest_points(bvh, prims, points, max_distance=inf, leaf="tri") -> hits   (nearest primitive per point, 3D)
     sphere_cast(bvh, prims, rays, radius, leaf="tri", robust=False) -> hits     (first contact of a ball swept along each ray, 3D)
+    tri_distance(bvh, tris9, query_tris, max_distance=inf) -> hits              (nearest mesh triangle to each query triangle / segment, 3D)
     radius_count / radius_search(bvh, prims, points, radius=r, leaf="tri")      (every primitive within r of each point, 3D)
     knn(bvh, prims, points, k, max_distance=inf, leaf="tri") -> ids, dist, counts (the k nearest primitives per point, sorted, 3D)
     winding_prepare(bvh, prims) -> moments; winding_numbers / occupancy / signed_distance(bvh, prims, moments, points, beta=2) (is a point inside the mesh, 3D)
@@ -23,5 +24,5 @@ Everything computes in hand-written HIP kernels through the C-ABI of libbvh_amd.
 """
 from .api import (BinnedSahBuilder, MiniTreeBuilder, SplitHeuristic, Bvh, Config, DefaultBuilder, Quality, RayFlags, SweepSahBuilder, ThreadPool, prepare_trace,  # noqa: F401
                   HITD, HITF, INVALID, NODED, NODEF, NODE2D, NODE2F, closest_points, hits_to_numpy, intersect, precompute_tris, sphere_bounds,
-                  tri_bounds, gather, radius_count, radius_search, offsets_from_counts, ray_hit_count, ray_hits, ray_hits_nearest, RAY_NEAREST_MAX_K, sphere_cast, knn, KNN_MAX_K, winding_prepare, winding_numbers, signed_distance, occupancy, overlap_count, overlap_search, self_overlaps, tri_intersect_count, tri_intersect_search, self_intersections, instance_prepare, intersect_instanced, std_sort_ids, radix_sort_pairs, radix_order, reinsertion_stats, last_optimize_profile, pinhole_rays, shade_eyelight)
+                  tri_bounds, gather, radius_count, radius_search, offsets_from_counts, ray_hit_count, ray_hits, ray_hits_nearest, RAY_NEAREST_MAX_K, sphere_cast, knn, KNN_MAX_K, winding_prepare, winding_numbers, signed_distance, occupancy, overlap_count, overlap_search, self_overlaps, tri_intersect_count, tri_intersect_search, self_intersections, tri_distance, instance_prepare, intersect_instanced, std_sort_ids, radix_sort_pairs, radix_order, reinsertion_stats, last_optimize_profile, pinhole_rays, shade_eyelight)
 from ._lib import BvhAmdError  # noqa: F401

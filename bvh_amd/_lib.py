@@ -160,6 +160,7 @@ _SIGS_T = {
     "bvh{S}_intersect_rays_nearest_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P]),
     "bvh{S}_sphere_cast_tri": (_I, [_P, _P, _P, _Z, _T, _P, _U, _P, _P, _P]),                 # (_T: the family's scalar, by value)
     "bvh{S}_sphere_cast_sphere": (_I, [_P, _P, _P, _Z, _T, _P, _U, _P, _P, _P]),
+    "bvh{S}_tri_distance": (_I, [_P, _P, _Z, _P, _Z, _T, _P, _U, _P, _P, _P, _P]),
     "bvh{S}_knn_tri": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_knn_sphere": (_I, [_P, _P, _P, _Z, _U, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_winding_prepare": (_I, [_P, _P, _P, _Z, _P]),
@@ -213,6 +214,7 @@ _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_inter
             "bvh{S}_intersect_rays_all_tri", "bvh{S}_intersect_rays_all_sphere",                      # and the all-hits ray queries
             "bvh{S}_intersect_rays_nearest_tri", "bvh{S}_intersect_rays_nearest_sphere",              # and the nearest-hits ray queries
             "bvh{S}_sphere_cast_tri", "bvh{S}_sphere_cast_sphere",                                    # and the sphere-cast queries
+            "bvh{S}_tri_distance",                                                                    # and the triangle-distance queries
             "bvh{S}_knn_tri", "bvh{S}_knn_sphere",                                                    # and the k-nearest queries
             "bvh{S}_winding_prepare", "bvh{S}_winding_numbers",                                       # and the winding numbers
             "bvh{S}_overlap_boxes", "bvh{S}_overlap_self",                                            # and the box-overlap queries

@@ -915,6 +915,46 @@ def tri_intersect_count(bvh: Bvh, tris9, query_tris, skip_shared: bool = False, 
     return (counts, cnt) if counters else counts
 
 
+def tri_distance(bvh: Bvh, tris9, query_tris, max_distance=float("inf"), original_ids: bool = False, sort_queries=None, counters: bool = False,
+                 out=None, query_uv: bool = False):
+    """For each query triangle, the nearest triangle of the tree, how far it is and where the two come closest (bvh3X_tri_distance).
+    tris9: (n_tris, 9) {p0, p1, p2} indexed by ORIGINAL primitive id, what refit_tris and tri_intersect_count take; query_tris: (n, 9)
+    in the same layout; a triangle with collinear or coincident vertices is the segment or point it is (a capsule against a mesh: query
+    the segment {a, b, b} and compare t with the radius). max_distance: a float for the whole batch, or an array / tensor of n.
+    Returns the (n, 4) tensor of hit records (hits_to_numpy views it), written into `out` if given: prim = BVH-order index
+    (bvh.prim_ids[i] with original_ids) or INVALID, t = the distance (0 for every pair tri_intersect_count counts; max_distance on a
+    miss), (u, v) = the barycentrics of the closest point on the tree triangle in closest_points' convention. With query_uv also the
+    (n, 2) barycentrics of the closest point on the query triangle (0 on a miss); with counters also (pairs, triangles fetched,
+    leaves). A NaN query coordinate, a NaN or negative max_distance: a miss. sort_queries: True / False force / forbid reordering
+    the batch internally (None: the library decides); records never change."""
+    torch = _torch()
+    t, q = _tri_intersect_args(bvh, tris9, query_tris, "tri_distance")
+    dt = q.dtype
+    n = q.shape[0]
+    limits = None
+    if isinstance(max_distance, (int, float)):
+        scalar = float(max_distance)
+    else:
+        scalar = 0.0
+        limits = _dev(max_distance)
+        if limits.dtype != dt:
+            raise TypeError("max_distance dtype must match the BVH scalar type")
+        if limits.dim() != 1 or limits.shape[0] != n:
+            raise ValueError(f"tri_distance: max_distance must be a float or hold one distance per query ({n}), got shape {tuple(limits.shape)}")
+    if out is None:
+        out = torch.empty((n, 4), dtype=dt, device=q.device)
+    elif out.dtype != dt or not out.is_contiguous() or out.numel() < n * 4:
+        raise TypeError("tri_distance: out must be a contiguous (n, 4) tensor of the BVH scalar type")
+    uv = torch.zeros((n, 2), dtype=dt, device=q.device) if query_uv else None
+    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_tri_distance")
+    _lib.check(fn(bvh._h, t.data_ptr(), t.shape[0], q.data_ptr(), n, scalar, limits.data_ptr() if limits is not None and n else None,
+                  int(_sort_flags(sort_queries, original_ids)), out.data_ptr(), uv.data_ptr() if query_uv and n else None,
+                  cnt.data_ptr() if counters else None, _stream()), "tri_distance")
+    res = (out,) + ((uv,) if query_uv else ()) + ((cnt,) if counters else ())
+    return res if len(res) > 1 else out
+
+
 def tri_intersect_search(bvh: Bvh, tris9, query_tris, max_per_query=None, original_ids: bool = False, skip_shared: bool = False, sort_queries=None,
                          counters: bool = False):
     """For each query triangle, the tree's triangles that intersect it (bvh3X_intersect_tris), in the order the tree fixes (depth-first,

@@ -629,6 +629,16 @@ int intersect_tris(const typename Family<T, 3>::Bvh* bvh, bool self, const T* d_
                                    static_cast<hipStream_t>(stream));
 }
 
+template <typename T>
+int tri_distance(const typename Family<T, 3>::Bvh* bvh, const T* d_tris9, size_t n_tris, const T* d_queries9, size_t n, T max_distance,
+                 const T* d_max_distances, unsigned flags, typename HitOf<T>::Type* d_hits, T* d_query_uv, bvh_amd_counters* d_counters, void* stream)
+{
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, n, "tri_distance", &b)) return rc;
+    return launch_tri_distance<T>(*b, d_tris9, n_tris, d_queries9, n, max_distance, d_max_distances, flags, d_hits, d_query_uv, d_counters,
+                                  static_cast<hipStream_t>(stream));
+}
+
 // bvh3X_instance_prepare / bvh3X_intersect_rays_instanced: struct bvh_amd_geometry3X is GeomRef<T> by layout (a handle is its BvhImpl).
 template <typename T, typename Geometry>
 const GeomRef<T>* geom_refs(const Geometry* geoms) {
@@ -898,6 +908,9 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_intersect_tris_self(const bvh##S* b, const T* tris9, size_t n_tris, unsigned flags, uint32_t* counts,   \
                                      const uint64_t* offsets, uint32_t* list_prims, bvh_amd_counters* cnt, void* s) {    \
         return intersect_tris<T>(b, true, tris9, n_tris, nullptr, 0, flags, counts, offsets, list_prims, cnt, s); }     \
+    int bvh##S##_tri_distance(const bvh##S* b, const T* tris9, size_t n_tris, const T* queries9, size_t n, T max_distance,            \
+                              const T* max_distances, unsigned flags, bvh_hit##S* hits, T* query_uv, bvh_amd_counters* cnt, void* s) { \
+        return tri_distance<T>(b, tris9, n_tris, queries9, n, max_distance, max_distances, flags, hits, query_uv, cnt, s); }          \
     int bvh##S##_instance_prepare(const bvh_amd_geometry##S* geoms, size_t n_geoms, const T* obj2world, const uint32_t* geometry,  \
                                   size_t n_instances, T* world2obj, T* bboxes, T* centers, void* s) {                    \
         return launch_instance_prepare<T>(geom_refs<T>(geoms), n_geoms, obj2world, geometry, n_instances, world2obj, bboxes, centers, \

@@ -284,6 +284,12 @@ int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_b
 template <typename T>
 int launch_tri_intersect(const BvhImpl<T>& b, bool self, const T* d_tris9, size_t n_tris, const T* d_queries9, size_t n, unsigned flags, uint32_t* d_counts,
                          const uint64_t* d_offsets, uint32_t* d_list_prims, bvh_amd_counters* d_counters, hipStream_t stream);
+// tri_distance.hip: batched triangle-distance queries, n x {p0.xyz, p1.xyz, p2.xyz} and a max_distance (d_max_distances[n], or
+// `max_distance` for all) against d_tris9[prim_ids[i]] -> per query the hit record of the nearest triangle and, with d_query_uv, the
+// barycentrics of the closest point on the query (flags: ORIGINAL_IDS, SORTED, UNSORTED)
+template <typename T>
+int launch_tri_distance(const BvhImpl<T>& b, const T* d_tris9, size_t n_tris, const T* d_queries9, size_t n, T max_distance, const T* d_max_distances,
+                        unsigned flags, typename HitOf<T>::Type* d_hits, T* d_query_uv, bvh_amd_counters* d_counters, hipStream_t stream);
 // ray_hits.hip: batched all-hits ray queries, n x {org, dir, tmin, tmax} -> per ray the count of primitives the unshortened ray crosses
 // and, with d_offsets, their hit records in the ray's segment [offsets[r], offsets[r + 1]) (flags: ROBUST, ORIGINAL_IDS, SORTED, UNSORTED)
 template <typename T>

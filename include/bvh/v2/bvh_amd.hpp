@@ -326,6 +326,7 @@ template <> struct Api<float, 3> {
     static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3f_intersect_rays_nearest_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, k, f, static_cast<bvh_hit3f*>(hits), counts, nullptr, nullptr); }
     static int sphere_cast_tri(const Handle* h, const void* prims, const void* rays, size_t n, float radius, const float* radii, unsigned f, void* hits) { return bvh3f_sphere_cast_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, radius, radii, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int sphere_cast_sphere(const Handle* h, const void* prims, const void* rays, size_t n, float radius, const float* radii, unsigned f, void* hits) { return bvh3f_sphere_cast_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, radius, radii, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
+    static int tri_distance(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, float max_distance, const float* max_distances, unsigned f, void* hits, float* query_uv) { return bvh3f_tri_distance(h, static_cast<const float*>(t9), nt, static_cast<const float*>(queries), n, max_distance, max_distances, f, static_cast<bvh_hit3f*>(hits), query_uv, nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
     static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh3f_winding_prepare(h, static_cast<const float*>(tris), static_cast<float*>(moments), rows, nullptr); }
@@ -379,6 +380,7 @@ template <> struct Api<double, 3> {
     static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3d_intersect_rays_nearest_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, k, f, static_cast<bvh_hit3d*>(hits), counts, nullptr, nullptr); }
     static int sphere_cast_tri(const Handle* h, const void* prims, const void* rays, size_t n, double radius, const double* radii, unsigned f, void* hits) { return bvh3d_sphere_cast_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, radius, radii, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int sphere_cast_sphere(const Handle* h, const void* prims, const void* rays, size_t n, double radius, const double* radii, unsigned f, void* hits) { return bvh3d_sphere_cast_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, radius, radii, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
+    static int tri_distance(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, double max_distance, const double* max_distances, unsigned f, void* hits, double* query_uv) { return bvh3d_tri_distance(h, static_cast<const double*>(t9), nt, static_cast<const double*>(queries), n, max_distance, max_distances, f, static_cast<bvh_hit3d*>(hits), query_uv, nullptr, nullptr); }
     static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
     static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh3d_winding_prepare(h, static_cast<const double*>(tris), static_cast<double*>(moments), rows, nullptr); }
@@ -1336,6 +1338,46 @@ void sphere_cast_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename N
     using T = typename Node::Scalar;
     static_assert(Node::dimension == 3, "sphere-cast queries: 3D trees only");
     detail::sphere_cast_host<T>(&Api<T, 3>::sphere_cast_sphere, bvh.device(), spheres.data(), rays, radius, detail::all_hits_flags<IsRobust>(flags), hits, "sphere_cast_sphere");
+}
+
+// For each query triangle, the nearest triangle of the tree, the distance and where the two come closest (include/bvh_amd.h:
+// bvh3X_tri_distance): one record {prim, t, u, v} per query, t the distance (0 for every pair intersect_tris_batch lists), (u, v) the
+// barycentrics of the closest point on the TREE triangle in closest_points_batch's convention, or {BVH_AMD_INVALID, max_distance, 0, 0};
+// `query_uv` (optional) receives the barycentrics {u, v} of the closest point on the QUERY triangle, two scalars per query. `tris` is
+// indexed by ORIGINAL primitive id, like refit_tris' and intersect_tris_batch's; a triangle with collinear or coincident vertices
+// stands for its segment or point. `max_distance` holds one scalar for the whole batch or one per query (a NaN or negative one: a
+// miss). `flags`: BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED.
+template <typename Node>
+void tri_distance_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, const DeviceArray<Tri<typename Node::Scalar, 3>>& queries,
+                        typename Node::Scalar max_distance, const DeviceArray<typename Node::Scalar>* max_distances, DeviceArray<Hit<typename Node::Scalar>>& hits,
+                        DeviceArray<typename Node::Scalar>* query_uv = nullptr, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "triangle-distance queries: 3D trees only");
+    const size_t n = queries.size();
+    if (hits.size() < n || (max_distances && max_distances->size() != n) || (query_uv && query_uv->size() < 2 * n))
+        throw Error("tri_distance: hits need n records, max_distances exactly n scalars, query_uv 2 n scalars");
+    check(Api<T, 3>::tri_distance(bvh.device(), tris.data(), tris.size(), queries.data(), n, max_distance, max_distances ? max_distances->data() : nullptr, flags,
+                                  hits.data(), query_uv ? query_uv->data() : nullptr), "tri_distance");
+}
+// Host form: uploads the queries (and the per-query distances), downloads the records (and the query barycentrics, if asked for).
+template <typename Node>
+void tri_distance_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, std::span<const Tri<typename Node::Scalar, 3>> queries,
+                        std::span<const typename Node::Scalar> max_distance, std::vector<Hit<typename Node::Scalar>>& hits,
+                        std::vector<typename Node::Scalar>* query_uv = nullptr, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "triangle-distance queries: 3D trees only");
+    const size_t n = queries.size();
+    if (max_distance.size() != 1 && max_distance.size() != n) throw Error("tri_distance: max_distance holds one scalar or one per query");
+    hits.resize(n);
+    if (query_uv) query_uv->resize(2 * n);
+    if (n == 0) return;
+    DeviceArray<Tri<T, 3>> d_queries(queries);
+    DeviceArray<Hit<T>> d_hits(n);
+    DeviceArray<T> d_uv(query_uv ? 2 * n : 1);
+    if (max_distance.size() == 1) { tri_distance_batch(bvh, tris, d_queries, max_distance[0], nullptr, d_hits, query_uv ? &d_uv : nullptr, flags); }
+    else { DeviceArray<T> d_max(max_distance); tri_distance_batch(bvh, tris, d_queries, T(0), &d_max, d_hits, query_uv ? &d_uv : nullptr, flags); }
+    d_hits.download(std::span<Hit<T>>(hits));
+    if (query_uv) d_uv.download(std::span<T>(*query_uv));
 }
 
 // Two-level scenes (include/bvh_amd.h: bvh3X_instance_prepare / bvh3X_intersect_rays_instanced): a table of geometries {tree, its

@@ -714,6 +714,44 @@ BVH_AMD_API int bvh3f_intersect_tris_self(const struct bvh3f*, const float* d_tr
 BVH_AMD_API int bvh3d_intersect_tris_self(const struct bvh3d*, const double* d_tris9, size_t n_tris, unsigned flags,
     uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, struct bvh_amd_counters* d_counters, void* stream);
 
+/* ---- batched triangle-distance queries: the nearest mesh triangle to a triangle ---------------------------------------------------- */
+/* d_tris9 as for bvh3X_intersect_tris (n_tris x {p0.xyz, p1.xyz, p2.xyz} by ORIGINAL primitive id, n_tris above the largest prim id);
+ * d_queries9 is n x 9 scalars in the same layout. A query also has a max_distance: d_max_distances[q] (n scalars, caller order) or,
+ * with d_max_distances == NULL, `max_distance` for the whole batch (INFINITY: unbounded). Triangles are closed sets; collinear or
+ * coincident vertices are legal on both sides and stand for the segment or point they are.
+ *   answer:  the tree triangle nearest to the query triangle within max_distance, as one record {prim, t, u, v}: t = the distance,
+ *            (u, v) = the barycentrics of the closest point on the TREE triangle in the convention of bvh3X_closest_points_*
+ *            (point = p0 + u (p1 - p0) + v (p2 - p0)). d_query_uv (optional, n x 2 scalars) receives the barycentrics of the closest
+ *            point on the QUERY triangle in the same convention: the two points give the separation vector and the contact normal.
+ *   t == 0:  for every pair bvh3X_intersect_tris' pair test accepts (run first, on the same vertices: the two queries cannot
+ *            disagree). The barycentrics then name a common point up to rounding: where an edge of one triangle crosses or touches
+ *            the other's face, or two edges cross. A segment that passes through a triangle also comes out at t ~ 0 (within the
+ *            tolerance), although the pair test, which wants area on both sides, does not see it.
+ *   else:    the smallest over the 9 edge / edge and the 6 vertex / face pairs, each computed as the distance of two points rebuilt
+ *            from clamped parameters: never the distance to a point outside a triangle; within the residual of INTEGRATION.md 3m.
+ *   miss:    {BVH_AMD_INVALID, max_distance, 0, 0} and query barycentrics 0: nothing within max_distance, a NaN query coordinate, a NaN
+ *            or negative max_distance.
+ *   ties:    among the triangles the walk tests, equal squared distances go to the lowest BVH-order index (also under
+ *            BVH_AMD_RAY_ORIGINAL_IDS, which maps the reported prim only). The walk enters a child iff the squared distance between
+ *            its box and the query triangle's box is <= the best squared distance so far, nearer first, and does not stop at 0. A
+ *            subtree whose box is computed to lie beyond the best distance is skipped, so, as for bvh3X_closest_points_*, the
+ *            record is the brute force's argmin by (distance^2, index) exactly when the arithmetic is exact, otherwise its distance
+ *            is within the stated residual of it.
+ *   flags:   BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED (bvh3X_intersect_tris' reordering key; with neither,
+ *            batches of >= 1M queries are reordered). Any other bit: BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * Outputs are in caller order. A query's record depends only on the tree, the triangles, the query, its max_distance and
+ * ORIGINAL_IDS: not on batch size, position or order, the reordering flags, the stream or the thread. d_counters (optional) receives
+ * {pair records fetched, leaf triangles fetched (before their box test), leaves visited}. Alignment: d_tris9, d_queries9,
+ * d_max_distances and d_query_uv to their scalar, d_hits 16 bytes, d_counters 8. Refused with BVH_AMD_ERR_ARG: a 2D tree, a NULL handle,
+ * a NULL d_tris9, d_queries9 or d_hits, a misaligned pointer, a tree without a device copy or without device prim ids, n_tris at or
+ * below the largest prim id. Re-entrant on a const tree (no work slot is claimed); like every reader of the tree, the caller orders
+ * it after a bvhXX_refit_*. Not offered: spheres, the 2D families, self-proximity with adjacency filtering, the k nearest triangles,
+ * all pairs within a distance, a dual-tree traversal. */
+BVH_AMD_API int bvh3f_tri_distance(const struct bvh3f*, const float* d_tris9, size_t n_tris, const float* d_queries9, size_t n, float max_distance,
+    const float* d_max_distances, unsigned flags, struct bvh_hit3f* d_hits, float* d_query_uv, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_tri_distance(const struct bvh3d*, const double* d_tris9, size_t n_tris, const double* d_queries9, size_t n, double max_distance,
+    const double* d_max_distances, unsigned flags, struct bvh_hit3d* d_hits, double* d_query_uv, struct bvh_amd_counters* d_counters, void* stream);
+
 /* ---- batched all-hits ray queries: for each ray, every primitive it crosses --------------------------------------------------------- */
 /* Rays and primitives as for bvh3X_intersect_rays_* (n x {org, dir, tmin, tmax}; BVH-order PrecomputedTri or Sphere<T, 3>).
  *   result:  every BVH-order index i that (1) passes the leaf test of bvh3X_intersect_rays_* (tri.h:56-74 / sphere.h:32-49) against
