@@ -16,6 +16,7 @@ Host-side mirror of the reference's interface for the hot path (names follow bvh
     winding_prepare(bvh, prims) -> moments; winding_numbers / occupancy / signed_distance(bvh, prims, moments, points, beta=2) (is a point inside the mesh, 3D)
     overlap_count / overlap_search(bvh, bboxes, query_boxes), self_overlaps(bvh, bboxes) (primitives whose boxes overlap a box; broad phase, 3D)
     tri_intersect_count / tri_intersect_search(bvh, tris9, query_tris), self_intersections(bvh, tris9) (triangles that intersect a triangle; narrow phase, 3D)
+    region_count / region_search(bvh, prims, planes, leaf="tri", exact=False), frustum_planes(eye, direction, up, fov_y, aspect, near, far) (primitives inside a set of planes: frusta, slabs, half-spaces, 3D)
     instance_prepare(geometries, transforms) / intersect_instanced(top, geometries, world2obj, rays) (two-level scenes of placed meshes, 3D)
     tri_bounds / precompute_tris / sphere_bounds                                (Tri::get_bbox, PrecomputedTri)
 
@@ -24,5 +25,5 @@ Everything computes in hand-written HIP kernels through the C-ABI of libbvh_amd.
 """
 from .api import (BinnedSahBuilder, MiniTreeBuilder, SplitHeuristic, Bvh, Config, DefaultBuilder, Quality, RayFlags, SweepSahBuilder, ThreadPool, prepare_trace,  # noqa: F401
                   HITD, HITF, INVALID, NODED, NODEF, NODE2D, NODE2F, closest_points, hits_to_numpy, intersect, precompute_tris, sphere_bounds,
-                  tri_bounds, gather, radius_count, radius_search, offsets_from_counts, ray_hit_count, ray_hits, ray_hits_nearest, RAY_NEAREST_MAX_K, sphere_cast, knn, KNN_MAX_K, winding_prepare, winding_numbers, signed_distance, occupancy, overlap_count, overlap_search, self_overlaps, tri_intersect_count, tri_intersect_search, self_intersections, tri_distance, instance_prepare, intersect_instanced, std_sort_ids, radix_sort_pairs, radix_order, reinsertion_stats, last_optimize_profile, pinhole_rays, shade_eyelight)
+                  tri_bounds, gather, radius_count, radius_search, offsets_from_counts, ray_hit_count, ray_hits, ray_hits_nearest, RAY_NEAREST_MAX_K, sphere_cast, knn, KNN_MAX_K, winding_prepare, winding_numbers, signed_distance, occupancy, overlap_count, overlap_search, self_overlaps, tri_intersect_count, tri_intersect_search, self_intersections, tri_distance, region_count, region_search, frustum_planes, REGION_MAX_PLANES, instance_prepare, intersect_instanced, std_sort_ids, radix_sort_pairs, radix_order, reinsertion_stats, last_optimize_profile, pinhole_rays, shade_eyelight)
 from ._lib import BvhAmdError  # noqa: F401

@@ -169,6 +169,8 @@ _SIGS_T = {
     "bvh{S}_overlap_self": (_I, [_P, _P, _Z, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_intersect_tris": (_I, [_P, _P, _Z, _P, _Z, _U, _P, _P, _P, _P, _P]),
     "bvh{S}_intersect_tris_self": (_I, [_P, _P, _Z, _U, _P, _P, _P, _P, _P]),
+    "bvh{S}_region_tris": (_I, [_P, _P, _Z, _P, _Z, _Z, _U, _P, _P, _P, _P, _P, _P]),
+    "bvh{S}_region_spheres": (_I, [_P, _P, _Z, _P, _Z, _Z, _U, _P, _P, _P, _P, _P, _P]),
     "bvh{S}_instance_prepare": (_I, [_P, _Z, _P, _P, _Z, _P, _P, _P, _P]),
     "bvh{S}_intersect_rays_instanced": (_I, [_P, _P, _Z, _P, _P, _Z, _P, _Z, _U, _P, _P, _P, _P]),
     # one ray, host leaf callback (c_api/bvh.h:277-295): (bvh, ray, callback struct)
@@ -219,6 +221,7 @@ _ONLY_3D = ("bvh_amd_tri_bounds{S}", "bvh_amd_precompute_tris{S}", "bvh{S}_inter
             "bvh{S}_winding_prepare", "bvh{S}_winding_numbers",                                       # and the winding numbers
             "bvh{S}_overlap_boxes", "bvh{S}_overlap_self",                                            # and the box-overlap queries
             "bvh{S}_intersect_tris", "bvh{S}_intersect_tris_self",                                    # and the triangle-intersection queries
+            "bvh{S}_region_tris", "bvh{S}_region_spheres",                                            # and the convex-region queries
             "bvh{S}_instance_prepare", "bvh{S}_intersect_rays_instanced",                             # and the instanced ray queries
             "bvh{S}_refit_tris", "bvh{S}_traversal_cost")                                             # (tri.h; the 3D area term)
 

@@ -915,6 +915,92 @@ def tri_intersect_count(bvh: Bvh, tris9, query_tris, skip_shared: bool = False, 
     return (counts, cnt) if counters else counts
 
 
+_REGION_EXACT = 64                                            # BVH_AMD_REGION_EXACT
+REGION_MAX_PLANES = 8
+
+
+def frustum_planes(eye, direction, up, fov_y, aspect, near, far, dtype=np.float32):
+    """The six planes {nx, ny, nz, d} of a view frustum, normals pointing OUT of it (a point x is inside iff n . x + d <= 0 for all
+    six), as a (6, 4) numpy array in the order near, far, left, right, bottom, top: what region_count / region_search take. The camera
+    is pinhole_rays': looking along `direction`, right = normalize(direction x up), the image's up = right x direction; fov_y is the
+    full vertical opening angle in radians and aspect = width / height of the opening (pinhole_rays' own frustum, whatever its
+    resolution, is fov_y = pi / 2, aspect = 1). The side planes pass through the eye; near and far are distances along `direction`.
+    Computed in float64 and rounded once to `dtype`."""
+    e = np.asarray(eye, dtype=np.float64).reshape(3)
+    d = np.asarray(direction, dtype=np.float64).reshape(3)
+    d = d / np.linalg.norm(d)
+    r = np.cross(d, np.asarray(up, dtype=np.float64).reshape(3))
+    r = r / np.linalg.norm(r)
+    u = np.cross(r, d)
+    ty = float(np.tan(0.5 * float(fov_y)))
+    tx = ty * float(aspect)
+    normals = [-d, d, -r - tx * d, r - tx * d, -u - ty * d, u - ty * d]
+    consts = [d @ e + float(near), -(d @ e) - float(far)] + [-(n @ e) for n in normals[2:]]
+    return np.ascontiguousarray(np.concatenate([np.stack(normals), np.asarray(consts)[:, None]], axis=1).astype(dtype))
+
+
+def _region_args(bvh: Bvh, prims, planes, leaf: str, exact: bool, who: str):
+    """The checks of the convex-region queries: ((n_prims, 9 or 4) primitives by original id, (n, m, 4) planes flattened to (n, 4 m), m)."""
+    torch = _torch()
+    if bvh.dim != 3:
+        raise TypeError(f"{who}: 3D trees only")
+    if leaf not in ("tri", "sphere"):
+        raise ValueError(f"{who}: leaf must be 'tri' or 'sphere'")
+    if exact and leaf != "tri":
+        raise ValueError(f"{who}: exact is a triangle test (spheres have the plane-by-plane test only)")
+    p = bvh._prims_in(prims, 9 if leaf == "tri" else 4, who)
+    if not hasattr(planes, "dtype"):
+        planes = np.asarray(planes)
+    if len(planes.shape) != 3 or planes.shape[2] != 4 or not 1 <= planes.shape[1] <= REGION_MAX_PLANES:
+        raise ValueError(f"{who}: planes must be (n, m, 4) with 1 <= m <= {REGION_MAX_PLANES}")
+    m = int(planes.shape[1])
+    if isinstance(planes, np.ndarray):
+        planes = torch.from_numpy(np.ascontiguousarray(planes))
+    q = bvh._prims_in(planes.reshape(planes.shape[0], 4 * m), 4 * m, who)
+    return p, q, m
+
+
+def region_count(bvh: Bvh, prims, planes, leaf: str = "tri", exact: bool = False, counters: bool = False):
+    """For each region (m planes {nx, ny, nz, d} with outward normals: the points with n . x + d <= 0 for all of them), how many of the
+    tree's primitives meet it (bvh3X_region_tris / bvh3X_region_spheres without lists): an int32 (n,) tensor; with counters also
+    (pairs, primitives tested, leaves). prims: (n_prims, 9) triangles {p0, p1, p2} (what refit_tris takes) or, with leaf="sphere",
+    (n_prims, 4) {centre, radius}, indexed by ORIGINAL primitive id; planes: (n, m, 4), 1 <= m <= 8 (pad with {0, 0, 0, 0}).
+    The default test rejects a primitive iff it lies wholly outside one plane, which also lists triangles beside an edge or corner of
+    the region; exact=True (triangles) lists exactly the triangles that share a point with the region. The batch is never reordered:
+    submit tiles in screen order."""
+    torch = _torch()
+    p, q, m = _region_args(bvh, prims, planes, leaf, exact, "region_count")
+    n = q.shape[0]
+    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
+    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_region_{'tris' if leaf == 'tri' else 'spheres'}")
+    _lib.check(fn(bvh._h, p.data_ptr(), p.shape[0], q.data_ptr(), m, n, _REGION_EXACT if exact else 0, counts.data_ptr(), None, None, None,
+                  cnt.data_ptr() if counters else None, _stream()), "region_count")
+    return (counts, cnt) if counters else counts
+
+
+def region_search(bvh: Bvh, prims, planes, leaf: str = "tri", exact: bool = False, max_per_query=None, original_ids: bool = False,
+                  inside: bool = False, counters: bool = False):
+    """For each region, the primitives that meet it (bvh3X_region_tris / bvh3X_region_spheres), in the order the tree fixes (depth-first,
+    left child first, ascending index inside a leaf); arguments as for region_count. Returns (offsets, ids) as overlap_search does:
+    offsets int64 (n + 1,), region q owns ids[offsets[q]:offsets[q + 1]] (int32 BVH-order indices, or bvh.prim_ids[i] with
+    original_ids). With inside=True a uint8 tensor parallel to ids follows: 1 = the primitive lies wholly inside the region, 0 = it
+    crosses the boundary (or is a padding slot).
+      max_per_query=None: exact lists - a count pass, the offsets on the device, one read of offsets[-1] to size the lists, a fill pass.
+      max_per_query=k: one pass, k slots per query (offsets = k * arange(n + 1)), unused slots holding -1 (INVALID); counts (int32,
+        untruncated) is appended, telling which lists overflowed.
+    With counters, (pairs, primitives tested, leaves) of the pass that wrote the lists is appended last."""
+    torch = _torch()
+    p, q, m = _region_args(bvh, prims, planes, leaf, exact, "region_search")
+    fn = getattr(_lib.load(), f"bvh{bvh._s}_region_{'tris' if leaf == 'tri' else 'spheres'}")
+    flags = (8 if original_ids else 0) | (_REGION_EXACT if exact else 0)
+    n = q.shape[0]
+    # (the inside flags take the place of radius_search's distances: one more array beside ids, written by the fill pass only)
+    call = lambda counts, offsets, ids, ins, cnt: fn(bvh._h, p.data_ptr(), p.shape[0], q.data_ptr(), m, n, flags, counts, offsets, ids, ins, cnt, _stream())
+    out = _two_pass_lists("region_search", call, n, q.device, max_per_query, counters, torch.uint8 if inside else None)
+    return out if inside else out[:2] + out[3:]
+
+
 def tri_distance(bvh: Bvh, tris9, query_tris, max_distance=float("inf"), original_ids: bool = False, sort_queries=None, counters: bool = False,
                  out=None, query_uv: bool = False):
     """For each query triangle, the nearest triangle of the tree, how far it is and where the two come closest (bvh3X_tri_distance).

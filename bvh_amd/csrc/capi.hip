@@ -639,6 +639,16 @@ int tri_distance(const typename Family<T, 3>::Bvh* bvh, const T* d_tris9, size_t
                                   static_cast<hipStream_t>(stream));
 }
 
+template <typename T>
+int region(const typename Family<T, 3>::Bvh* bvh, int leaf, const T* d_prims, size_t n_prims, const T* d_planes, size_t m, size_t n, unsigned flags,
+           uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, uint8_t* d_list_inside, bvh_amd_counters* d_counters, void* stream)
+{
+    const BvhImpl<T>* b = nullptr;
+    if (const int rc = point_query_tree<T>(bvh, n, leaf == LEAF_TRIANGLE ? "region_tris" : "region_spheres", &b)) return rc;
+    return launch_region<T>(*b, leaf, d_prims, n_prims, d_planes, m, n, flags, d_counts, d_offsets, d_list_prims, d_list_inside, d_counters,
+                            static_cast<hipStream_t>(stream));
+}
+
 // bvh3X_instance_prepare / bvh3X_intersect_rays_instanced: struct bvh_amd_geometry3X is GeomRef<T> by layout (a handle is its BvhImpl).
 template <typename T, typename Geometry>
 const GeomRef<T>* geom_refs(const Geometry* geoms) {
@@ -911,6 +921,12 @@ void bvh_thread_pool_destroy(bvh_thread_pool* p) { delete reinterpret_cast<Threa
     int bvh##S##_tri_distance(const bvh##S* b, const T* tris9, size_t n_tris, const T* queries9, size_t n, T max_distance,            \
                               const T* max_distances, unsigned flags, bvh_hit##S* hits, T* query_uv, bvh_amd_counters* cnt, void* s) { \
         return tri_distance<T>(b, tris9, n_tris, queries9, n, max_distance, max_distances, flags, hits, query_uv, cnt, s); }          \
+    int bvh##S##_region_tris(const bvh##S* b, const T* tris9, size_t n_tris, const T* planes, size_t m, size_t n, unsigned flags,     \
+                             uint32_t* counts, const uint64_t* offsets, uint32_t* list_prims, uint8_t* list_inside, bvh_amd_counters* cnt, void* s) { \
+        return region<T>(b, LEAF_TRIANGLE, tris9, n_tris, planes, m, n, flags, counts, offsets, list_prims, list_inside, cnt, s); }   \
+    int bvh##S##_region_spheres(const bvh##S* b, const T* sph4, size_t n_sph, const T* planes, size_t m, size_t n, unsigned flags,    \
+                                uint32_t* counts, const uint64_t* offsets, uint32_t* list_prims, uint8_t* list_inside, bvh_amd_counters* cnt, void* s) { \
+        return region<T>(b, LEAF_SPHERE, sph4, n_sph, planes, m, n, flags, counts, offsets, list_prims, list_inside, cnt, s); }       \
     int bvh##S##_instance_prepare(const bvh_amd_geometry##S* geoms, size_t n_geoms, const T* obj2world, const uint32_t* geometry,  \
                                   size_t n_instances, T* world2obj, T* bboxes, T* centers, void* s) {                    \
         return launch_instance_prepare<T>(geom_refs<T>(geoms), n_geoms, obj2world, geometry, n_instances, world2obj, bboxes, centers, \

@@ -290,6 +290,13 @@ int launch_tri_intersect(const BvhImpl<T>& b, bool self, const T* d_tris9, size_
 template <typename T>
 int launch_tri_distance(const BvhImpl<T>& b, const T* d_tris9, size_t n_tris, const T* d_queries9, size_t n, T max_distance, const T* d_max_distances,
                         unsigned flags, typename HitOf<T>::Type* d_hits, T* d_query_uv, bvh_amd_counters* d_counters, hipStream_t stream);
+// region.hip: batched convex-region queries, n x m planes {nx, ny, nz, d} (1 <= m <= 8) against d_prims[prim_ids[i]] (triangles of 9
+// scalars or spheres of 4, n_prims by original id), output as launch_overlap plus d_list_inside (optional, with d_offsets: one byte
+// per list entry, 1 = wholly inside); flags: ORIGINAL_IDS, REGION_EXACT (triangles only). The batch is never reordered.
+template <typename T>
+int launch_region(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, size_t n_prims, const T* d_planes, size_t m, size_t n, unsigned flags,
+                  uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, uint8_t* d_list_inside, bvh_amd_counters* d_counters,
+                  hipStream_t stream);
 // ray_hits.hip: batched all-hits ray queries, n x {org, dir, tmin, tmax} -> per ray the count of primitives the unshortened ray crosses
 // and, with d_offsets, their hit records in the ray's segment [offsets[r], offsets[r + 1]) (flags: ROBUST, ORIGINAL_IDS, SORTED, UNSORTED)
 template <typename T>

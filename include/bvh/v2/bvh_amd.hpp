@@ -333,6 +333,8 @@ template <> struct Api<float, 3> {
     static int winding_numbers(const Handle* h, const void* tris, const void* moments, size_t rows, const void* queries, size_t n, double beta, unsigned f, void* w, void* hits) { return bvh3f_winding_numbers(h, static_cast<const float*>(tris), static_cast<const float*>(moments), rows, static_cast<const float*>(queries), n, beta, f, static_cast<float*>(w), static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_boxes(h, static_cast<const float*>(bb), nb, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_self(h, static_cast<const float*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
+    static int region_tris(const Handle* h, const void* t9, size_t nt, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh3f_region_tris(h, static_cast<const float*>(t9), nt, static_cast<const float*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); }
+    static int region_spheres(const Handle* h, const void* s4, size_t ns, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh3f_region_spheres(h, static_cast<const float*>(s4), ns, static_cast<const float*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); }
     static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_intersect_tris(h, static_cast<const float*>(t9), nt, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int intersect_tris_self(const Handle* h, const void* t9, size_t nt, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_intersect_tris_self(h, static_cast<const float*>(t9), nt, f, counts, offsets, list, nullptr, nullptr); }
     using CGeometry = bvh_amd_geometry3f;
@@ -387,6 +389,8 @@ template <> struct Api<double, 3> {
     static int winding_numbers(const Handle* h, const void* tris, const void* moments, size_t rows, const void* queries, size_t n, double beta, unsigned f, void* w, void* hits) { return bvh3d_winding_numbers(h, static_cast<const double*>(tris), static_cast<const double*>(moments), rows, static_cast<const double*>(queries), n, beta, f, static_cast<double*>(w), static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
     static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_boxes(h, static_cast<const double*>(bb), nb, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_self(h, static_cast<const double*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
+    static int region_tris(const Handle* h, const void* t9, size_t nt, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh3d_region_tris(h, static_cast<const double*>(t9), nt, static_cast<const double*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); }
+    static int region_spheres(const Handle* h, const void* s4, size_t ns, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh3d_region_spheres(h, static_cast<const double*>(s4), ns, static_cast<const double*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); }
     static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_intersect_tris(h, static_cast<const double*>(t9), nt, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
     static int intersect_tris_self(const Handle* h, const void* t9, size_t nt, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_intersect_tris_self(h, static_cast<const double*>(t9), nt, f, counts, offsets, list, nullptr, nullptr); }
     using CGeometry = bvh_amd_geometry3d;
@@ -1147,6 +1151,93 @@ void intersect_tris_self_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typen
     static_assert(Node::dimension == 3, "triangle-intersection queries: 3D trees only");
     detail::overlap_host([&](uint32_t* c, const uint64_t* o, uint32_t* l) {
         return Api<T, 3>::intersect_tris_self(bvh.device(), tris.data(), tris.size(), flags, c, o, l); }, bvh.prim_ids.size(), offsets, list_prims, "intersect_tris_self");
+}
+
+// For each region - the points inside all of m planes {n, d}, n . x + d <= 0, 1 <= m <= 8, outward normals - every primitive of the
+// tree that meets it (include/bvh_amd.h: bvh3X_region_tris / bvh3X_region_spheres), in the order the tree fixes: a view or tile frustum,
+// a slab, a half-space. `planes` holds regions x m planes, region after region; pad a region with {0, 0, 0, 0}. `tris` / `spheres` are
+// indexed by ORIGINAL primitive id, like refit_tris'. By default a primitive is rejected iff it lies wholly outside one plane, which
+// also lists triangles beside an edge or corner of the region; with BVH_AMD_REGION_EXACT in `flags` (triangles only) exactly the
+// triangles that share a point with the region are listed. The outputs and the device and host forms are those of
+// overlap_boxes_batch, plus `list_inside` (optional, beside list_prims): 1 = the primitive lies wholly inside the region. The batch is
+// never reordered: submit tiles in screen order.
+template <typename T>
+struct RegionPlane { T nx, ny, nz, d; };
+
+namespace detail {
+template <typename Call>
+void region_device(Call call, size_t planes, size_t m, DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims,
+                   DeviceArray<uint8_t>* list_inside, const char* what) {
+    if (m == 0 || planes % m) throw Error(std::string(what) + ": planes must hold a whole number of regions of m planes");
+    const size_t n = planes / m;
+    if ((counts && counts->size() < n) || (offsets && offsets->size() < n + 1)) throw Error(std::string(what) + ": counts need n entries, offsets n + 1");
+    if (list_inside && list_prims && list_inside->size() < list_prims->size()) throw Error(std::string(what) + ": list_inside needs an entry per list entry");
+    check(call(n, counts ? counts->data() : nullptr, offsets ? offsets->data() : nullptr, list_prims ? list_prims->data() : nullptr,
+               list_inside ? list_inside->data() : nullptr), what);
+}
+// count, offsets on the device, one read of offsets[n] to size the lists, fill
+template <typename Call>
+void region_host(Call call, size_t planes, size_t m, std::vector<uint64_t>& offsets, std::vector<uint32_t>& list_prims, std::vector<uint8_t>* list_inside,
+                 const char* what) {
+    if (m == 0 || planes % m) throw Error(std::string(what) + ": planes must hold a whole number of regions of m planes");
+    const size_t n = planes / m;
+    offsets.assign(n + 1, 0);
+    list_prims.clear();
+    if (list_inside) list_inside->clear();
+    if (n == 0) return;
+    DeviceArray<uint32_t> d_counts(n);
+    DeviceArray<uint64_t> d_offsets(n + 1);
+    region_device(call, planes, m, &d_counts, nullptr, nullptr, nullptr, what);
+    check(bvh_amd_offsets_from_counts(d_counts.data(), n, d_offsets.data(), nullptr), "offsets_from_counts");
+    d_offsets.download(std::span<uint64_t>(offsets));
+    const size_t total = static_cast<size_t>(offsets[n]);
+    list_prims.resize(total);
+    if (list_inside) list_inside->resize(total);
+    if (total == 0) return;
+    DeviceArray<uint32_t> d_list(total);
+    DeviceArray<uint8_t> d_inside(list_inside ? total : 1);
+    region_device(call, planes, m, nullptr, &d_offsets, &d_list, list_inside ? &d_inside : nullptr, what);
+    d_list.download(std::span<uint32_t>(list_prims));
+    if (list_inside) d_inside.download(std::span<uint8_t>(*list_inside));
+}
+} // namespace detail
+
+template <typename Node>
+void region_tris_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, const DeviceArray<RegionPlane<typename Node::Scalar>>& planes,
+                       size_t m, DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims,
+                       DeviceArray<uint8_t>* list_inside = nullptr, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "region queries: 3D trees only");
+    detail::region_device([&](size_t n, uint32_t* c, const uint64_t* o, uint32_t* l, uint8_t* i) {
+        return Api<T, 3>::region_tris(bvh.device(), tris.data(), tris.size(), planes.data(), m, n, flags, c, o, l, i); }, planes.size(), m, counts, offsets, list_prims, list_inside, "region_tris");
+}
+// Host form: exact lists. Region q's triangles are list_prims[offsets[q] .. offsets[q + 1]) (and their flags in *list_inside).
+template <typename Node>
+void region_tris_batch(const Bvh<Node>& bvh, const DeviceArray<Tri<typename Node::Scalar, 3>>& tris, std::span<const RegionPlane<typename Node::Scalar>> planes,
+                       size_t m, std::vector<uint64_t>& offsets, std::vector<uint32_t>& list_prims, std::vector<uint8_t>* list_inside = nullptr, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "region queries: 3D trees only");
+    DeviceArray<RegionPlane<T>> d_planes(planes);
+    detail::region_host([&](size_t n, uint32_t* c, const uint64_t* o, uint32_t* l, uint8_t* i) {
+        return Api<T, 3>::region_tris(bvh.device(), tris.data(), tris.size(), d_planes.data(), m, n, flags, c, o, l, i); }, planes.size(), m, offsets, list_prims, list_inside, "region_tris");
+}
+template <typename Node>
+void region_spheres_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, const DeviceArray<RegionPlane<typename Node::Scalar>>& planes,
+                          size_t m, DeviceArray<uint32_t>* counts, const DeviceArray<uint64_t>* offsets, DeviceArray<uint32_t>* list_prims,
+                          DeviceArray<uint8_t>* list_inside = nullptr, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "region queries: 3D trees only");
+    detail::region_device([&](size_t n, uint32_t* c, const uint64_t* o, uint32_t* l, uint8_t* i) {
+        return Api<T, 3>::region_spheres(bvh.device(), spheres.data(), spheres.size(), planes.data(), m, n, flags, c, o, l, i); }, planes.size(), m, counts, offsets, list_prims, list_inside, "region_spheres");
+}
+template <typename Node>
+void region_spheres_batch(const Bvh<Node>& bvh, const DeviceArray<Sphere<typename Node::Scalar, 3>>& spheres, std::span<const RegionPlane<typename Node::Scalar>> planes,
+                          size_t m, std::vector<uint64_t>& offsets, std::vector<uint32_t>& list_prims, std::vector<uint8_t>* list_inside = nullptr, unsigned flags = 0u) {
+    using T = typename Node::Scalar;
+    static_assert(Node::dimension == 3, "region queries: 3D trees only");
+    DeviceArray<RegionPlane<T>> d_planes(planes);
+    detail::region_host([&](size_t n, uint32_t* c, const uint64_t* o, uint32_t* l, uint8_t* i) {
+        return Api<T, 3>::region_spheres(bvh.device(), spheres.data(), spheres.size(), d_planes.data(), m, n, flags, c, o, l, i); }, planes.size(), m, offsets, list_prims, list_inside, "region_spheres");
 }
 
 // For each ray, every primitive the UNSHORTENED ray crosses (include/bvh_amd.h: bvh3X_intersect_rays_all_*): what Bvh::intersect<false,

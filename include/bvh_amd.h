@@ -120,8 +120,10 @@ enum bvh_amd_ray_flags {
                                 /* (SORTED / UNSORTED / ORIGINAL_IDS apply to bvhXX_closest_points_* and bvhXX_radius_search_* queries too) */
     BVH_AMD_RAY_ORIGINAL_IDS = 8u, /* hit.prim = the ORIGINAL primitive id bvh.prim_ids[i] (what c_api_example.c:265-268 looks up per
                                       hit) instead of the BVH-order index i: one more pass over the hit records, on the device    */
-    BVH_AMD_TRI_SKIP_SHARED = 32u  /* bvh3X_intersect_tris / bvh3X_intersect_tris_self only (every other entry point refuses it): a
+    BVH_AMD_TRI_SKIP_SHARED = 32u, /* bvh3X_intersect_tris / bvh3X_intersect_tris_self only (every other entry point refuses it): a
                                       pair of triangles with a common vertex is not listed                                       */
+    BVH_AMD_REGION_EXACT = 64u     /* bvh3X_region_tris only (every other entry point refuses it): list a triangle iff it shares a
+                                      point with the region, not merely iff no single plane rejects it                          */
 };
 
 /* Which reference builder a device build reproduces (bit-exact node/prim order). */
@@ -751,6 +753,67 @@ BVH_AMD_API int bvh3f_tri_distance(const struct bvh3f*, const float* d_tris9, si
     const float* d_max_distances, unsigned flags, struct bvh_hit3f* d_hits, float* d_query_uv, struct bvh_amd_counters* d_counters, void* stream);
 BVH_AMD_API int bvh3d_tri_distance(const struct bvh3d*, const double* d_tris9, size_t n_tris, const double* d_queries9, size_t n, double max_distance,
     const double* d_max_distances, unsigned flags, struct bvh_hit3d* d_hits, double* d_query_uv, struct bvh_amd_counters* d_counters, void* stream);
+
+/* ---- batched convex-region queries: the primitives inside a set of planes ---------------------------------------------------------- */
+/* A query is m planes {nx, ny, nz, d}, 1 <= m <= 8, m one number for the whole batch: d_planes is n x m x 4 scalars of the tree's type.
+ * d_tris9 as for bvh3X_intersect_tris (n_prims x {p0.xyz, p1.xyz, p2.xyz} by ORIGINAL primitive id); d_sph4 is n_prims x {centre.xyz,
+ * radius} by original id. n_prims must exceed the largest prim id.
+ *   value:   of plane p at a point x: ((nx*x0 + ny*x1) + nz*x2) + d, evaluated in exactly this order with one rounding per operation
+ *            and no contraction.
+ *   region:  x is inside plane p iff value <= 0 (a NaN value is not inside); the region is the set of points inside all m planes:
+ *            closed, possibly unbounded, possibly empty. Normals point OUT of the region and need not have unit length. A plane with
+ *            a zero normal and d <= 0 holds everywhere (that is how a caller pads to m), one with d > 0 nowhere. -0 equals +0. A query
+ *            with a NaN or infinite plane component has an empty list.
+ *   CULL:    (triangles, the default) a triangle is rejected iff some plane has none of its three vertices inside. Conservative: a
+ *            superset of the triangles that meet the region (a triangle beside an edge or corner of the region can pass every plane
+ *            on its own); exact for one plane, for parallel planes and for triangles with a vertex in the region.
+ *   EXACT:   (triangles, BVH_AMD_REGION_EXACT) a triangle matches iff triangle and region share a point as CLOSED sets, decided by
+ *            SIGNS of 3 x 3 determinants only. With D[p][i] the value of plane p at vertex i, plane p is, in the triangle's (u, v)
+ *            parameters, the constraint L_p = (D[p][1] - D[p][0], D[p][2] - D[p][0], D[p][0]), read a*u + b*v + c <= 0; the triangle
+ *            adds (-1, 0, 0), (0, -1, 0) and (1, 1, -1). The m + 3 half-planes share a point iff for some pair i < j,
+ *            w = cross(L_i, L_j).z != 0 and every other k has sign(w) * dot(L_k, cross(L_i, L_j)) <= 0 (a nonempty bounded polygon
+ *            has a vertex). No division, no epsilon, no product of two determinants: where every determinant is computed without
+ *            rounding the answer is the exact one, otherwise it is the one these roundings give, the same on the device and in a
+ *            host build of the same source. A triangle without area needs no special case. A triangle with a NaN or infinite
+ *            coefficient in some L_p (a NaN vertex, an overflow) is not listed. EXACT runs only on triangles that pass CULL: its list
+ *            is a subset of CULL's.
+ *   spheres: per plane len = sqrt((nx*nx + ny*ny) + nz*nz), s = the value at the centre; the sphere is outside plane p iff
+ *            !(s <= r*len) and is listed iff it is outside no plane; it is wholly inside iff s <= -(r*len) for every plane. The
+ *            plane-by-plane test only: BVH_AMD_REGION_EXACT is refused for spheres.
+ *   result:  every BVH-order index i whose primitive passes its test and all of whose ancestors' boxes pass the node test: for every
+ *            plane, the value at the box corner lowest along the normal (max on an axis where the normal's component is < 0, min
+ *            otherwise; the same expression as a vertex's value; per axis the kernel takes the smaller of n*min and n*max, which for
+ *            finite bounds is that product) is <= 0. Rounding is monotone, so that value is <= the value at
+ *            every finite point of the box: for a tree fitted to finite triangles (built from bvh_amd_tri_bounds3X of them, or
+ *            bvh3X_refit_tris with them) the result is EXACTLY the brute-force set of the triangle test. A sphere's box is c +- r
+ *            after rounding and the sphere test has r*len where the box has r*|n|_1: a sphere within rounding of tangent from outside
+ *            can be dropped by the node test. The walk never drops a sphere whose margin r*len - s, evaluated in float64, exceeds
+ *            16 u M, u = the unit roundoff of the tree's type, M = |nx|(|cx| + r) + |ny|(|cy| + r) + |nz|(|cz| + r) + |d|
+ *            (DESIGN.md has the argument). For primitives the tree was not fitted to the result is the walk's set.
+ *   order, output: those of bvh3X_overlap_boxes: depth-first, left child before right, ascending index inside a leaf; d_counts[q] is
+ *            never truncated; query q owns [d_offsets[q], d_offsets[q + 1]) of d_list_prims (required iff d_offsets), the rest of a
+ *            segment is padded with BVH_AMD_INVALID, nothing outside a segment is written, a non-ascending segment is empty. At least
+ *            one of d_counts and d_offsets must be given. d_list_inside (optional, only with d_offsets) is parallel to d_list_prims:
+ *            1 = wholly inside the region (all three vertices inside all planes, or the sphere rule above), 0 = crossing; padding 0.
+ *   flags:   BVH_AMD_RAY_ORIGINAL_IDS lists prim_ids[i]; BVH_AMD_REGION_EXACT (triangles). The batch is NEVER reordered: an unbounded
+ *            region has no cell, so BVH_AMD_RAY_SORTED and BVH_AMD_RAY_UNSORTED are refused; callers get coherence by submitting
+ *            tiles in screen order. Any other bit: BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ * Outputs are in caller order. A query's result does not depend on batch size, position, stream or thread. d_counters (optional)
+ * receives {pair records fetched, primitives tested, leaves visited}. Alignment: d_prims and d_planes to their scalar, d_offsets and
+ * d_counters 8 bytes, d_counts and d_list_prims 4. Refused with BVH_AMD_ERR_ARG: a 2D tree, a NULL handle, a NULL or misaligned
+ * pointer, the forbidden output combinations, d_list_inside without d_offsets, a tree without a device copy or without device prim
+ * ids, n_prims at or below the largest prim id, m outside 1..8, BVH_AMD_REGION_EXACT on spheres. Re-entrant on a const tree (no work
+ * slot is claimed); like every reader of the tree, the caller orders it after a bvhXX_refit_*. One lane walks one region and lists
+ * its whole output serially: the mapping is for many regions. Not offered: the 2D families, exact sphere-against-polytope tests,
+ * boxes as primitives, more than 8 planes, plane masking down the tree, a wave-per-query walk for a single huge region. */
+BVH_AMD_API int bvh3f_region_tris(const struct bvh3f*, const float* d_tris9, size_t n_prims, const float* d_planes, size_t m, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, uint8_t* d_list_inside, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_region_tris(const struct bvh3d*, const double* d_tris9, size_t n_prims, const double* d_planes, size_t m, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, uint8_t* d_list_inside, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3f_region_spheres(const struct bvh3f*, const float* d_sph4, size_t n_prims, const float* d_planes, size_t m, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, uint8_t* d_list_inside, struct bvh_amd_counters* d_counters, void* stream);
+BVH_AMD_API int bvh3d_region_spheres(const struct bvh3d*, const double* d_sph4, size_t n_prims, const double* d_planes, size_t m, size_t n, unsigned flags,
+    uint32_t* d_counts, const uint64_t* d_offsets, uint32_t* d_list_prims, uint8_t* d_list_inside, struct bvh_amd_counters* d_counters, void* stream);
 
 /* ---- batched all-hits ray queries: for each ray, every primitive it crosses --------------------------------------------------------- */
 /* Rays and primitives as for bvh3X_intersect_rays_* (n x {org, dir, tmin, tmax}; BVH-order PrecomputedTri or Sphere<T, 3>).
