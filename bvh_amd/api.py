@@ -495,9 +495,8 @@ def intersect(bvh: Bvh, prims, rays, any_hit: bool = False, robust: bool = False
     if r.dtype != dt or p.dtype != dt:
         raise TypeError("prims/rays dtype must match the BVH scalar type")
     n = r.shape[0]
-    if out is None:
-        out = torch.empty((n, 4), dtype=dt, device=r.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
+    out = _records_out(out, n, dt, r.device)
+    cnt = _counters(counters, r.device)
     flags = (RayFlags.ANY_HIT if any_hit else 0) | (RayFlags.ROBUST if robust else 0) | (0 if sort_rays is None else RayFlags.SORTED if sort_rays else RayFlags.UNSORTED) | \
             (8 if original_ids else 0)                        # BVH_AMD_RAY_ORIGINAL_IDS: hit.prim = bvh.prim_ids[BVH-order index]
     fn = getattr(lib, f"bvh{s}_intersect_rays_{'tri' if leaf == 'tri' else 'sphere'}")
@@ -519,12 +518,10 @@ def closest_points(bvh: Bvh, prims, points, max_distance: float = float("inf"), 
     it): prim = BVH-order index (bvh.prim_ids[i] with original_ids) or INVALID, t = distance (max_distance on a miss), (u, v) the
     barycentrics of the closest point of a triangle (point = p0 + u (p1 - p0) + v (p2 - p0); 0 for spheres); with counters also
     (pairs, tests, leaves). sort_queries: True / False force / forbid reordering the batch internally (None: the library decides)."""
-    torch = _torch()
     q, p, dt = _point_query_args(bvh, prims, points, max_distance, leaf, "closest_points", "max_distance", float("inf"))
     n = q.shape[0]
-    if out is None:
-        out = torch.empty((n, 4), dtype=dt, device=q.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    out = _records_out(out, n, dt, q.device)
+    cnt = _counters(counters, q.device)
     fn = getattr(_lib.load(), f"bvh{bvh._s}_closest_points_{leaf}")
     _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, int(_sort_flags(sort_queries, original_ids)), out.data_ptr(), cnt.data_ptr() if counters else None, _stream()),
                "closest_points")
@@ -568,6 +565,35 @@ def _sort_flags(sort_queries, original_ids=False):
     return (0 if sort_queries is None else RayFlags.SORTED if sort_queries else RayFlags.UNSORTED) | (8 if original_ids else 0)
 
 
+def _counters(counters: bool, dev):
+    """The (pairs, tests, leaves) tensor a query fills when asked for counters, else None."""
+    torch = _torch()
+    return torch.zeros(3, dtype=torch.int64, device=dev) if counters else None
+
+
+def _records_out(out, n: int, dt, dev, who=None):
+    """`out` as given, or allocated: the contiguous (n, 4) tensor of hit records of the tree's scalar type. `who` names the function
+    that checks a given `out` (intersect and closest_points take it as it comes)."""
+    if out is None:
+        return _torch().empty((n, 4), dtype=dt, device=dev)
+    if who is not None and (out.dtype != dt or not out.is_contiguous() or out.numel() < n * 4):
+        raise TypeError(f"{who}: out must be a contiguous (n, 4) tensor of the BVH scalar type")
+    return out
+
+
+def _per_query_value(value, n: int, dt, who: str, name: str, one: str):
+    """A float for the batch, or one value per query: (scalar, None) or (0.0, the (n,) device tensor). `name` is the argument, `one`
+    what it holds ("radius per ray")."""
+    if isinstance(value, (int, float)):
+        return float(value), None
+    values = _dev(value)
+    if values.dtype != dt:
+        raise TypeError(f"{name} dtype must match the BVH scalar type")
+    if values.dim() != 1 or values.shape[0] != n:
+        raise ValueError(f"{who}: {name} must be a float or hold one {one} ({n}), got shape {tuple(values.shape)}")
+    return 0.0, values
+
+
 def winding_prepare(bvh: Bvh, prims, out=None):
     """The per-node moments the winding-number queries read (bvh3X_winding_prepare): a (node_count + 1, 8) tensor of the tree's scalar
     type, node c in row c + 1 as {cx, cy, cz, r2, Nx, Ny, Nz, area}, written into `out` if given. prims: the BVH-order (n, 12)
@@ -596,7 +622,7 @@ def _winding_call(bvh: Bvh, p, moments, q, beta, sort_queries, counters: bool, o
     n = q.shape[0]
     if out is None:
         out = torch.empty(n, dtype=q.dtype, device=q.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    cnt = _counters(counters, q.device)
     fn = getattr(_lib.load(), f"bvh{bvh._s}_winding_numbers")
     _lib.check(fn(bvh._h, p.data_ptr(), m.data_ptr(), m.numel() // 8, q.data_ptr(), n, float(beta), int(_sort_flags(sort_queries)), out.data_ptr(),
                   hits.data_ptr() if hits is not None else None, cnt.data_ptr() if counters else None, _stream()), who)
@@ -646,15 +672,12 @@ def offsets_from_counts(counts):
 def radius_count(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", sort_queries=None, counters: bool = False):
     """For each point, how many primitives lie within the radius (bvhXX_radius_search_* without lists): an int32 (n,) tensor; with
     counters also (pairs, tests, leaves). points: (n, 3) with the scalar radius, or (n, 4) with a per-query radius in column 3."""
-    torch = _torch()
     q, p, _ = _point_query_args(bvh, prims, points, radius, leaf, "radius_count")
     n = q.shape[0]
-    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
     fn = getattr(_lib.load(), f"bvh{bvh._s}_radius_search_{leaf}")
-    _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, int(_sort_flags(sort_queries)), counts.data_ptr(), None, None, None,
-                  cnt.data_ptr() if counters else None, _stream()), "radius_count")
-    return (counts, cnt) if counters else counts
+    flags = int(_sort_flags(sort_queries))
+    call = lambda counts, offsets, ids, dist, cnt: fn(bvh._h, p.data_ptr(), q.data_ptr(), n, flags, counts, offsets, ids, dist, cnt, _stream())
+    return _count_only("radius_count", call, n, q.device, counters)
 
 
 def radius_search(bvh: Bvh, prims, points, radius=None, leaf: str = "tri", max_per_query=None, distances: bool = True,
@@ -683,7 +706,7 @@ def _two_pass_lists(who: str, call, n: int, dev, max_per_query, counters: bool, 
     dist_dtype) is written beside ids. With record_dtype the list is ONE array of hit records, (total, 4) of that scalar type, in
     the place of ids."""
     torch = _torch()
-    cnt = torch.zeros(3, dtype=torch.int64, device=dev) if counters else None
+    cnt = _counters(counters, dev)
     counts = torch.zeros(n, dtype=torch.int32, device=dev)
     if max_per_query is None:
         _lib.check(call(counts.data_ptr(), None, None, None, None), who)
@@ -707,6 +730,15 @@ def _two_pass_lists(who: str, call, n: int, dev, max_per_query, counters: bool, 
     return out + (cnt,) if counters else out
 
 
+def _count_only(who: str, call, n: int, dev, counters: bool):
+    """The count pass of call(counts, offsets, ids, dist, counters) alone, no lists: the int32 (n,) counts[, counters]."""
+    torch = _torch()
+    counts = torch.zeros(n, dtype=torch.int32, device=dev)
+    cnt = _counters(counters, dev)
+    _lib.check(call(counts.data_ptr(), None, None, None, cnt.data_ptr() if counters else None), who)
+    return (counts, cnt) if counters else counts
+
+
 def _ray_query_args(bvh: Bvh, prims, rays, leaf: str, who: str):
     """The checks of the all-hits ray queries: ((n, 8) rays, prims, scalar dtype)."""
     torch = _torch()
@@ -725,16 +757,12 @@ def _ray_query_args(bvh: Bvh, prims, rays, leaf: str, who: str):
 def ray_hit_count(bvh: Bvh, prims, rays, leaf: str = "tri", robust: bool = False, sort_queries=None, counters: bool = False):
     """For each ray, how many primitives the unshortened ray crosses (bvh3X_intersect_rays_all_* without lists): an int32 (n,)
     tensor; with counters also (pairs, tests, leaves). prims and rays as for intersect."""
-    torch = _torch()
     r, p, _ = _ray_query_args(bvh, prims, rays, leaf, "ray_hit_count")
     n = r.shape[0]
-    counts = torch.zeros(n, dtype=torch.int32, device=r.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
     fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_rays_all_{leaf}")
     flags = int(_sort_flags(sort_queries)) | (int(RayFlags.ROBUST) if robust else 0)
-    _lib.check(fn(bvh._h, p.data_ptr(), r.data_ptr(), n, flags, counts.data_ptr(), None, None, cnt.data_ptr() if counters else None, _stream()),
-               "ray_hit_count")
-    return (counts, cnt) if counters else counts
+    call = lambda counts, offsets, hits, _, cnt: fn(bvh._h, p.data_ptr(), r.data_ptr(), n, flags, counts, offsets, hits, cnt, _stream())
+    return _count_only("ray_hit_count", call, n, r.device, counters)
 
 
 def ray_hits(bvh: Bvh, prims, rays, leaf: str = "tri", robust: bool = False, max_per_ray=None, original_ids: bool = False, sort_queries=None,
@@ -780,7 +808,7 @@ def ray_hits_nearest(bvh: Bvh, prims, rays, k: int, leaf: str = "tri", robust: b
     n = r.shape[0]
     hits = torch.empty((n, k, 4), dtype=dt, device=r.device)
     counts = torch.zeros(n, dtype=torch.int32, device=r.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
+    cnt = _counters(counters, r.device)
     fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_rays_nearest_{leaf}")
     flags = int(_sort_flags(sort_queries, original_ids)) | (int(RayFlags.ROBUST) if robust else 0)
     _lib.check(fn(bvh._h, p.data_ptr(), r.data_ptr(), n, k, flags, hits.data_ptr(), counts.data_ptr(), cnt.data_ptr() if counters else None, _stream()),
@@ -800,24 +828,11 @@ def sphere_cast(bvh: Bvh, prims, rays, radius, leaf: str = "tri", robust: bool =
     a miss. robust=True takes the robust box test: wanted for axis-parallel sweeps (a direction component of exactly 0), which the
     fast test loses as intersect's does. With counters also (pairs, tests, leaves). sort_queries: True / False force / forbid reordering the batch internally
     (None: the library decides); records never change."""
-    torch = _torch()
     r, p, dt = _ray_query_args(bvh, prims, rays, leaf, "sphere_cast")
     n = r.shape[0]
-    radii = None
-    if isinstance(radius, (int, float)):
-        scalar = float(radius)
-    else:
-        scalar = 0.0
-        radii = _dev(radius)
-        if radii.dtype != dt:
-            raise TypeError("radius dtype must match the BVH scalar type")
-        if radii.dim() != 1 or radii.shape[0] != n:
-            raise ValueError(f"sphere_cast: radius must be a float or hold one radius per ray ({n}), got shape {tuple(radii.shape)}")
-    if out is None:
-        out = torch.empty((n, 4), dtype=dt, device=r.device)
-    elif out.dtype != dt or not out.is_contiguous() or out.numel() < n * 4:
-        raise TypeError("sphere_cast: out must be a contiguous (n, 4) tensor of the BVH scalar type")
-    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
+    scalar, radii = _per_query_value(radius, n, dt, "sphere_cast", "radius", "radius per ray")
+    out = _records_out(out, n, dt, r.device, "sphere_cast")
+    cnt = _counters(counters, r.device)
     fn = getattr(_lib.load(), f"bvh{bvh._s}_sphere_cast_{leaf}")
     flags = int(_sort_flags(sort_queries, original_ids)) | (int(RayFlags.ROBUST) if robust else 0)
     _lib.check(fn(bvh._h, p.data_ptr(), r.data_ptr(), n, scalar, radii.data_ptr() if radii is not None and n else None, flags, out.data_ptr(),
@@ -838,15 +853,12 @@ def overlap_count(bvh: Bvh, bboxes, query_boxes, sort_queries=None, counters: bo
     """For each query box, how many primitives' boxes overlap it (bvh3X_overlap_boxes without lists): an int32 (n,) tensor; with
     counters also (pairs, box tests, leaves). bboxes: (n_boxes, 6) {min, max} indexed by ORIGINAL primitive id, what the builders and
     refit_boxes take; query_boxes: (n, 6) in the same layout. Closed intervals: touching boxes overlap."""
-    torch = _torch()
     bb, q = _overlap_args(bvh, bboxes, query_boxes, "overlap_count")
-    n = q.shape[0]
-    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
     fn = getattr(_lib.load(), f"bvh{bvh._s}_overlap_boxes")
-    _lib.check(fn(bvh._h, bb.data_ptr(), bb.shape[0], q.data_ptr(), n, int(_sort_flags(sort_queries)), counts.data_ptr(), None, None,
-                  cnt.data_ptr() if counters else None, _stream()), "overlap_count")
-    return (counts, cnt) if counters else counts
+    flags = int(_sort_flags(sort_queries))
+    n = q.shape[0]
+    call = lambda counts, offsets, ids, _, cnt: fn(bvh._h, bb.data_ptr(), bb.shape[0], q.data_ptr(), n, flags, counts, offsets, ids, cnt, _stream())
+    return _count_only("overlap_count", call, n, q.device, counters)
 
 
 def overlap_search(bvh: Bvh, bboxes, query_boxes, max_per_query=None, original_ids: bool = False, sort_queries=None, counters: bool = False):
@@ -903,16 +915,12 @@ def tri_intersect_count(bvh: Bvh, tris9, query_tris, skip_shared: bool = False, 
     tensor; with counters also (pairs, triangles fetched, leaves). tris9: (n_tris, 9) {p0, p1, p2} indexed by ORIGINAL primitive id,
     what refit_tris takes; query_tris: (n, 9) in the same layout. Closed sets: touching triangles intersect; a triangle without area
     or with a NaN or infinite coordinate intersects nothing. skip_shared: pairs with a common vertex are not counted."""
-    torch = _torch()
     t, q = _tri_intersect_args(bvh, tris9, query_tris, "tri_intersect_count")
-    n = q.shape[0]
-    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
     fn = getattr(_lib.load(), f"bvh{bvh._s}_intersect_tris")
     flags = int(_sort_flags(sort_queries)) | (_TRI_SKIP_SHARED if skip_shared else 0)
-    _lib.check(fn(bvh._h, t.data_ptr(), t.shape[0], q.data_ptr(), n, flags, counts.data_ptr(), None, None,
-                  cnt.data_ptr() if counters else None, _stream()), "tri_intersect_count")
-    return (counts, cnt) if counters else counts
+    n = q.shape[0]
+    call = lambda counts, offsets, ids, _, cnt: fn(bvh._h, t.data_ptr(), t.shape[0], q.data_ptr(), n, flags, counts, offsets, ids, cnt, _stream())
+    return _count_only("tri_intersect_count", call, n, q.device, counters)
 
 
 _REGION_EXACT = 64                                            # BVH_AMD_REGION_EXACT
@@ -968,15 +976,12 @@ def region_count(bvh: Bvh, prims, planes, leaf: str = "tri", exact: bool = False
     The default test rejects a primitive iff it lies wholly outside one plane, which also lists triangles beside an edge or corner of
     the region; exact=True (triangles) lists exactly the triangles that share a point with the region. The batch is never reordered:
     submit tiles in screen order."""
-    torch = _torch()
     p, q, m = _region_args(bvh, prims, planes, leaf, exact, "region_count")
-    n = q.shape[0]
-    counts = torch.zeros(n, dtype=torch.int32, device=q.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
     fn = getattr(_lib.load(), f"bvh{bvh._s}_region_{'tris' if leaf == 'tri' else 'spheres'}")
-    _lib.check(fn(bvh._h, p.data_ptr(), p.shape[0], q.data_ptr(), m, n, _REGION_EXACT if exact else 0, counts.data_ptr(), None, None, None,
-                  cnt.data_ptr() if counters else None, _stream()), "region_count")
-    return (counts, cnt) if counters else counts
+    flags = _REGION_EXACT if exact else 0
+    n = q.shape[0]
+    call = lambda counts, offsets, ids, ins, cnt: fn(bvh._h, p.data_ptr(), p.shape[0], q.data_ptr(), m, n, flags, counts, offsets, ids, ins, cnt, _stream())
+    return _count_only("region_count", call, n, q.device, counters)
 
 
 def region_search(bvh: Bvh, prims, planes, leaf: str = "tri", exact: bool = False, max_per_query=None, original_ids: bool = False,
@@ -1017,22 +1022,10 @@ def tri_distance(bvh: Bvh, tris9, query_tris, max_distance=float("inf"), origina
     t, q = _tri_intersect_args(bvh, tris9, query_tris, "tri_distance")
     dt = q.dtype
     n = q.shape[0]
-    limits = None
-    if isinstance(max_distance, (int, float)):
-        scalar = float(max_distance)
-    else:
-        scalar = 0.0
-        limits = _dev(max_distance)
-        if limits.dtype != dt:
-            raise TypeError("max_distance dtype must match the BVH scalar type")
-        if limits.dim() != 1 or limits.shape[0] != n:
-            raise ValueError(f"tri_distance: max_distance must be a float or hold one distance per query ({n}), got shape {tuple(limits.shape)}")
-    if out is None:
-        out = torch.empty((n, 4), dtype=dt, device=q.device)
-    elif out.dtype != dt or not out.is_contiguous() or out.numel() < n * 4:
-        raise TypeError("tri_distance: out must be a contiguous (n, 4) tensor of the BVH scalar type")
+    scalar, limits = _per_query_value(max_distance, n, dt, "tri_distance", "max_distance", "distance per query")
+    out = _records_out(out, n, dt, q.device, "tri_distance")
     uv = torch.zeros((n, 2), dtype=dt, device=q.device) if query_uv else None
-    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    cnt = _counters(counters, q.device)
     fn = getattr(_lib.load(), f"bvh{bvh._s}_tri_distance")
     _lib.check(fn(bvh._h, t.data_ptr(), t.shape[0], q.data_ptr(), n, scalar, limits.data_ptr() if limits is not None and n else None,
                   int(_sort_flags(sort_queries, original_ids)), out.data_ptr(), uv.data_ptr() if query_uv and n else None,
@@ -1154,7 +1147,7 @@ def intersect_instanced(top: Bvh, geometries, world2obj, rays, geometry_ids=None
     elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() == 4 * n):
         raise TypeError("intersect_instanced: `out` must be a contiguous (n, 4) device tensor of the trees' scalar type")
     inst = torch.empty(n, dtype=torch.int32, device=r.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=r.device) if counters else None
+    cnt = _counters(counters, r.device)
     flags = (RayFlags.ANY_HIT if any_hit else 0) | (RayFlags.ROBUST if robust else 0) | (8 if original_ids else 0)
     fn = getattr(_lib.load(), f"bvh{s}_intersect_rays_instanced")
     _lib.check(fn(top._h, table, len(table), w.data_ptr(), gid.data_ptr() if gid is not None else None, n_inst, r.data_ptr(), n, int(flags),
@@ -1185,7 +1178,7 @@ def knn(bvh: Bvh, prims, points, k: int, max_distance: float = float("inf"), lea
     ids = torch.empty((n, k), dtype=torch.int32, device=q.device)
     dist = torch.empty((n, k), dtype=dt, device=q.device) if distances else None
     counts = torch.zeros(n, dtype=torch.int32, device=q.device)
-    cnt = torch.zeros(3, dtype=torch.int64, device=q.device) if counters else None
+    cnt = _counters(counters, q.device)
     fn = getattr(_lib.load(), f"bvh{bvh._s}_knn_{leaf}")
     _lib.check(fn(bvh._h, p.data_ptr(), q.data_ptr(), n, k, int(_sort_flags(sort_queries, original_ids)), ids.data_ptr(),
                   dist.data_ptr() if distances else None, counts.data_ptr(), cnt.data_ptr() if counters else None, _stream()), "knn")

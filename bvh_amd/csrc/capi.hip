@@ -389,15 +389,7 @@ int refit_prims(BvhImpl<T>* pb, int src_kind, const T* d_src, size_t n_src, T* d
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (const int rc = on_current_device(b, who)) return rc;
     if (b.node_count == 0 || !b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH has no device copy");
-    if (b.max_prim_id < 0) {
-        uint32_t largest = 0;
-        const int rc = max_prim_id_device(b.d_prim_ids, b.prim_count, stream, &largest);
-        if (rc) return rc;
-        b.max_prim_id = largest;
-    }
-    if (b.prim_count && n_src <= static_cast<size_t>(b.max_prim_id.load()))
-        return fail(BVH_AMD_ERR_ARG, std::string(who) + ": " + std::to_string(n_src) + " primitives given, but prim_ids refers to primitive " +
-                    std::to_string(b.max_prim_id.load()) + " (the array is indexed by original primitive id)");
+    if (const int rc = source_array_check(b, n_src, "primitives", who, stream)) return rc;
     // (no wait for an earlier refit_*'s root copy here: note_refit() below supersedes it, and the host blocks on nothing in the steady
     //  state; the mirror can only be valid after sync_host(), which has waited)
     const bool from_host = b.host_valid || !b.d_nodes || b.d_nodes_count != b.node_count;

@@ -1,6 +1,7 @@
 // Per-lane body of the batched closest-point query (closest.hip): one query's load, its two tests and its record around
-// nearest_walk.inc, the pruned depth-first walk through the pair records that knn_body.inc and ray_nearest_body.inc also run. The query
-// load and the distance functions are point_walk.inc's. Kept as an include so that tests/cpp/closest_body_host.cpp
+// nearest_walk.inc, the pruned depth-first walk through the pair records that ray_nearest_body.inc, sphere_cast_body.inc and
+// tri_distance_body.inc also run (knn_body.inc holds a copy of it); the LDS tier of its stack, kClosestLds, was measured on this query
+// and stands beside the walk. The query load and the distance functions are point_walk.inc's. Kept as an include so that tests/cpp/closest_body_host.cpp
 // compiles the very same text for the host (one emulated lane per query). Expects what point_walk.inc expects, and store_hit.
 #pragma once
 
@@ -9,12 +10,6 @@
 namespace bvh_amd {
 
 namespace {
-
-// Stack entries of a lane held in LDS ({node word, box distance^2} in two [depth][lane] arrays), the rest in scratch and HBM
-// (point_walk.inc has the tiers). 8 entries in LDS (16 KB per block of float queries, 24 KB of double: 7 / 5-6 waves per
-// SIMD, the VGPRs' limit) against 16 (5 / 3 waves, bound by LDS): 2^24 uniform queries on the 1M soup 12.10 -> 10.46 ms, on 1M f64
-// spheres 15.10 -> 13.24 ms (DESIGN.md, "Closest-point queries").
-constexpr int kClosestLds = 8;
 
 template <typename T>
 struct ClosestArgs : PointArgs<T> {

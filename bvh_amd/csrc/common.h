@@ -409,6 +409,10 @@ template <typename T>
 int refit_prims_device(HostNode<T>* d_nodes, PairNode<T>* d_pairs, size_t node_count, int src_kind, const T* d_src, size_t n_src,
                        const uint32_t* d_prim_ids, size_t prim_count, hipStream_t stream);
 int max_prim_id_device(const uint32_t* d_prim_ids, size_t prim_count, hipStream_t stream, uint32_t* out);
+// The largest prim id of a tree: BvhImpl::max_prim_id, or one read-back on `stream` that fills it (once per layout, whoever asks first).
+template <typename T> int largest_prim_id(const BvhImpl<T>& b, hipStream_t stream, long long* out);
+// A caller's array of n_src `noun` ("boxes", "triangles", "primitives") indexed by ORIGINAL primitive id must reach the largest one.
+template <typename T> int source_array_check(const BvhImpl<T>& b, size_t n_src, const char* noun, const std::string& who, hipStream_t stream);
 template <typename T> int traversal_cost(const BvhImpl<T>& b, double* cost_out, hipStream_t stream);   // upload.hip
 
 } // namespace bvh_amd

@@ -163,12 +163,8 @@ int launch_instanced(const BvhImpl<T>& top, const GeomRef<T>* geoms, size_t n_ge
         misaligned(d_counters, 8))
         return fail(BVH_AMD_ERR_ARG, who + ": device pointers must be 16-byte aligned (hit instances and geometry indices 4, counters 8)");
     if (top.node_count == 0 || !top.d_prim_ids || (top.pair_count && !top.d_pairs)) return fail(BVH_AMD_ERR_ARG, who + ": the top BVH has no device copy");
-    long long largest = top.max_prim_id.load();
-    if (largest < 0) {                                        // one read-back per layout, shared with refit_boxes / the overlap queries
-        uint32_t found = 0;
-        if (const int rc = max_prim_id_device(top.d_prim_ids, top.prim_count, stream, &found)) return rc;
-        top.max_prim_id = largest = found;
-    }
+    long long largest = 0;                                    // (cached per layout, shared with source_array_check's callers)
+    if (const int rc = largest_prim_id(top, stream, &largest)) return rc;
     if (top.prim_count && n_instances <= static_cast<size_t>(largest))
         return fail(BVH_AMD_ERR_ARG, who + ": " + std::to_string(n_instances) + " instances given, but the top tree's prim_ids refer to instance " +
                     std::to_string(largest));

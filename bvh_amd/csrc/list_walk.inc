@@ -1,7 +1,9 @@
-// What the per-lane bodies of the list queries share (radius_body.inc, overlap_body.inc, ray_hits_body.inc): the output arguments, and the one walk
+// What the per-lane bodies of the list queries share (radius_body.inc, overlap_body.inc, tri_intersect_body.inc, region_body.inc,
+// ray_hits_body.inc): the output arguments, and the one walk
 // that counts every match of a query and lists the first of them in the query's segment of a caller-sized buffer. The bodies supply
 // the query, the two tests and the stores. Kept as an include so that the host harnesses (tests/cpp/radius_body_host.cpp,
-// overlap_body_host.cpp, ray_hits_body_host.cpp) compile the very same text, through the bodies. Expects what point_walk.inc expects.
+// overlap_body_host.cpp, tri_intersect_body_host.cpp, region_body_host.cpp, ray_hits_body_host.cpp) compile the very same text,
+// through the bodies. Expects what point_walk.inc expects.
 #pragma once
 
 #include "point_walk.inc"

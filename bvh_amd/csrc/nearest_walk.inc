@@ -1,11 +1,13 @@
-// What the per-lane bodies of the nearest queries share (closest_body.inc, ray_nearest_body.inc; knn_body.inc holds a copy of this
-// text, for a measured reason it states): the one walk that
+// What the per-lane bodies of the nearest queries share (closest_body.inc, ray_nearest_body.inc, sphere_cast_body.inc,
+// tri_distance_body.inc; knn_body.inc holds a copy of this text, for a measured reason it states): the one walk that
 // visits the nearer child first, stacks the farther one with its key and drops whatever lies beyond a limit the caller lowers as it
-// finds primitives. A key is a box's squared distance to the query point, or the t at which a ray enters it; the limit is the best
-// squared distance so far (closest), or the key of the worst of the k candidates held (knn, nearest-hits: knn_heap.inc). The bodies
+// finds primitives. A key is a box's squared distance to the query point or to the query triangle's box, or the t at which a ray
+// enters it (grown by the ball's radius: sphere-cast); the limit is the best squared distance or contact so far (closest,
+// tri-distance, sphere-cast), or the key of the worst of the k candidates held (knn, nearest-hits: knn_heap.inc). The bodies
 // supply the query, the two tests and the write-out. It is the keyed counterpart of list_walk.inc, which prunes nothing and stacks
-// node words alone. Kept as an include so that the host harnesses (tests/cpp/closest_body_host.cpp,
-// ray_nearest_body_host.cpp) compile the very same text, through the bodies. Expects what point_walk.inc expects.
+// node words alone. Also here: kClosestLds, the LDS tier of the stack that closest, sphere-cast and tri-distance size by. Kept as an
+// include so that the host harnesses (tests/cpp/closest_body_host.cpp, ray_nearest_body_host.cpp, sphere_cast_body_host.cpp,
+// tri_distance_body_host.cpp) compile the very same text, through the bodies. Expects what point_walk.inc expects.
 #pragma once
 
 #include "point_walk.inc"
@@ -13,6 +15,12 @@
 namespace bvh_amd {
 
 namespace {
+
+// Stack entries of a lane held in LDS ({node word, box distance^2} in two [depth][lane] arrays), the rest in scratch and HBM
+// (point_walk.inc has the tiers). 8 entries in LDS (16 KB per block of float queries, 24 KB of double: 7 / 5-6 waves per
+// SIMD, the VGPRs' limit) against 16 (5 / 3 waves, bound by LDS): 2^24 uniform queries on the 1M soup 12.10 -> 10.46 ms, on 1M f64
+// spheres 15.10 -> 13.24 ms (DESIGN.md, "Closest-point queries").
+constexpr int kClosestLds = 8;
 
 // One query, one lane: depth-first walk from the root. nodes(lb, rb, kl, kr, hl, hr) tests the two child boxes of a record
 // ({minx, maxx, miny, maxy, minz, maxz} each) against the query and the limit as it stands: the children's keys and whether each is

@@ -52,16 +52,7 @@ int launch_overlap(const BvhImpl<T>& b, bool self, const T* d_bboxes, size_t n_b
     const char* fault = list_output_fault(d_counts, d_offsets, d_list_prims, nullptr);
     if (!fault && !aligned) fault = "device pointers must be aligned (boxes and queries to their scalar, offsets and counters 8 bytes, counts and list prims 4)";
     if (const int rc = point_query_check(b, n, flags, d_bboxes && (self || d_queries6), fault, who); rc || n == 0) return rc;
-    if (!b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH has no device prim ids");
-    long long largest = b.max_prim_id.load();
-    if (largest < 0) {                                        // one read-back per layout, shared with refit_boxes / refit_tris
-        uint32_t found = 0;
-        if (const int rc = max_prim_id_device(b.d_prim_ids, b.prim_count, stream, &found)) return rc;
-        b.max_prim_id = largest = found;
-    }
-    if (b.prim_count && n_boxes <= static_cast<size_t>(largest))
-        return fail(BVH_AMD_ERR_ARG, std::string(who) + ": " + std::to_string(n_boxes) + " boxes given, but prim_ids refers to primitive " +
-                    std::to_string(largest) + " (the array is indexed by original primitive id)");
+    if (const int rc = source_array_check(b, n_boxes, "boxes", who, stream)) return rc;
     const unsigned run_flags = self ? flags | BVH_AMD_RAY_UNSORTED : flags;
     return point_query_run<T, kQueryBoxes>(b, d_bboxes, d_queries6, n, run_flags, d_counters, sizeof(uint32_t), kBlock, kPointSortMin, kPointKeyBits, who, stream,
                                     [&](const PointArgs<T>& args, T*) {

@@ -3,6 +3,7 @@
 // primitive id (what bvhXX_build_device and bvhXX_refit_boxes take): the box of BVH-order primitive i is bboxes[box_ids[i]], so the
 // query does not care what kind of primitive the tree was built over. In self mode the query IS BVH-order primitive `slot` and only
 // i > slot is listed: every unordered overlapping pair once.
+// The box tests (load_box6, node_overlaps, box_overlaps) are point_walk.inc's, where tri_pair.inc and tri_intersect_body.inc find them too.
 // Kept as an include so that tests/cpp/overlap_body_host.cpp compiles the very same text for the host (one emulated lane per query).
 // Expects what point_walk.inc expects.
 #pragma once
@@ -19,29 +20,6 @@ template <typename T>
 struct OverlapArgs : ListArgs<T> {           // prims = the boxes, n_boxes x {min.xyz, max.xyz} by original id; queries = n x the same (null: self mode)
     const uint32_t* box_ids;                   // BVH-order index -> original id (always; prim_ids is set only to REPORT original ids)
 };
-
-// A box {min.xyz, max.xyz} of the caller's arrays (aligned to its scalar only).
-template <typename T>
-__device__ inline void load_box6(const T* p, T (&lo)[3], T (&hi)[3]) {
-    lo[0] = p[0]; lo[1] = p[1]; lo[2] = p[2];
-    hi[0] = p[3]; hi[1] = p[4]; hi[2] = p[5];
-}
-
-// Closed intervals on one axis: [lo, hi] is the query's, already known to be proper (lo <= hi); [bmin, bmax] overlaps it iff it is
-// proper itself and neither lies wholly before the other. A NaN makes the comparison it is part of false; -0 equals +0.
-template <typename T>
-__device__ inline bool axis_overlaps(T bmin, T bmax, T lo, T hi) { return bmin <= hi && lo <= bmax && bmin <= bmax; }
-
-// The one test of the walk, for a child's box of a pair record {minx, maxx, miny, maxy, minz, maxz} ...
-template <typename T>
-__device__ inline bool node_overlaps(const T (&b)[6], const T (&lo)[3], const T (&hi)[3]) {
-    return axis_overlaps(b[0], b[1], lo[0], hi[0]) && axis_overlaps(b[2], b[3], lo[1], hi[1]) && axis_overlaps(b[4], b[5], lo[2], hi[2]);
-}
-// ... and for a primitive's box {min.xyz}, {max.xyz}.
-template <typename T>
-__device__ inline bool box_overlaps(const T (&bl)[3], const T (&bh)[3], const T (&lo)[3], const T (&hi)[3]) {
-    return axis_overlaps(bl[0], bh[0], lo[0], hi[0]) && axis_overlaps(bl[1], bh[1], lo[1], hi[1]) && axis_overlaps(bl[2], bh[2], lo[2], hi[2]);
-}
 
 // One query, one lane: list_walk (which has the order of the walk and the shape of the output), a child entered iff its box overlaps
 // the query, every primitive whose box overlaps a match, the unused rest of a segment padded with BVH_AMD_INVALID.

@@ -1,4 +1,6 @@
-// The launch path of the batched point, box and ray list / row queries (closest.hip, radius.hip, knn.hip, overlap.hip, ray_hits.hip, ray_nearest.hip), once: the thresholds, the
+// The launch path of the batched point, box, triangle, region and ray list / row queries (closest.hip, radius.hip, knn.hip, overlap.hip,
+// tri_intersect.hip, tri_distance.hip, region.hip, winding.hip, ray_hits.hip, ray_nearest.hip, sphere_cast.hip; instanced.hip takes
+// its thresholds, misaligned, the launch and the counter epilogue), once: the thresholds, the
 // argument checks they share, the driver (counters, depth pass, HBM spill, reading order, launches), the output check and the Fill
 // switch of the list queries, and the kernels' counter epilogue. Expects common.h,
 // trace_device.h, ray_key.h, query_order.h and the kind's body (point_walk.inc: PointArgs) to have been included.

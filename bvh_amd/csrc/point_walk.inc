@@ -1,8 +1,11 @@
-// What the per-lane bodies of the point, box and ray-list queries share (knn_body.inc; through nearest_walk.inc closest_body.inc and
-// ray_nearest_body.inc; through list_walk.inc radius_body.inc, overlap_body.inc and ray_hits_body.inc): the arguments common to their kernels, the query load, the squared distance of a point to one primitive — a PrecomputedTri {p0, e1 = p0 - p1, e2 = p2 - p0, n}
-// or a Sphere {c, r} — and to a box, the streaming stores of the outputs and the index arithmetic of the walk's three-tier stack. Kept as an
+// What the per-lane bodies of the point, box, triangle, region and ray-list queries share (knn_body.inc, winding_body.inc,
+// instanced_body.inc; through nearest_walk.inc closest_body.inc, ray_nearest_body.inc, sphere_cast_body.inc and tri_distance_body.inc;
+// through list_walk.inc radius_body.inc, overlap_body.inc, tri_intersect_body.inc, region_body.inc and ray_hits_body.inc; tri_pair.inc):
+// the arguments common to their kernels, the query load, the squared distance of a point to one primitive — a PrecomputedTri
+// {p0, e1 = p0 - p1, e2 = p2 - p0, n} or a Sphere {c, r} — and to a box, the closed box-overlap tests, the streaming stores of the
+// outputs (list entries, hit records) and the index arithmetic of the walk's three-tier stack. Kept as an
 // include so that the host harnesses (tests/cpp/*_body_host.cpp) compile the very same text, through the bodies, with one emulated lane
-// per query. Expects trace_device.h (Num, dot3, load_pair, load_prim12, load_prim4, kBlock) and common.h, or the harnesses' stand-ins
+// per query. Expects trace_device.h (Num, dot3, load_pair, load_prim12, load_prim4, store_hit, store_hit_nt, kBlock) and common.h, or the harnesses' stand-ins
 // for it (tests/cpp/host_lane_prelude.h: PairNode, HitOf, kCountBits, kCountMask, LEAF_*). Compiled with -ffp-contract=off on both
 // sides: one rounding per operation, division and square root correctly rounded, so host and device produce the same bits.
 #pragma once
@@ -112,6 +115,29 @@ __device__ inline T box_dist2(const T (&b)[6], const T (&q)[3]) {
     return dot3(e[0], e[1], e[2], e[0], e[1], e[2]);
 }
 
+// A box {min.xyz, max.xyz} of the caller's arrays (aligned to its scalar only).
+template <typename T>
+__device__ inline void load_box6(const T* p, T (&lo)[3], T (&hi)[3]) {
+    lo[0] = p[0]; lo[1] = p[1]; lo[2] = p[2];
+    hi[0] = p[3]; hi[1] = p[4]; hi[2] = p[5];
+}
+
+// Closed intervals on one axis: [lo, hi] is the query's, already known to be proper (lo <= hi); [bmin, bmax] overlaps it iff it is
+// proper itself and neither lies wholly before the other. A NaN makes the comparison it is part of false; -0 equals +0.
+template <typename T>
+__device__ inline bool axis_overlaps(T bmin, T bmax, T lo, T hi) { return bmin <= hi && lo <= bmax && bmin <= bmax; }
+
+// The one test of the walk, for a child's box of a pair record {minx, maxx, miny, maxy, minz, maxz} ...
+template <typename T>
+__device__ inline bool node_overlaps(const T (&b)[6], const T (&lo)[3], const T (&hi)[3]) {
+    return axis_overlaps(b[0], b[1], lo[0], hi[0]) && axis_overlaps(b[2], b[3], lo[1], hi[1]) && axis_overlaps(b[4], b[5], lo[2], hi[2]);
+}
+// ... and for a primitive's box {min.xyz}, {max.xyz}.
+template <typename T>
+__device__ inline bool box_overlaps(const T (&bl)[3], const T (&bh)[3], const T (&lo)[3], const T (&hi)[3]) {
+    return axis_overlaps(bl[0], bh[0], lo[0], hi[0]) && axis_overlaps(bl[1], bh[1], lo[1], hi[1]) && axis_overlaps(bl[2], bh[2], lo[2], hi[2]);
+}
+
 // Squared distance from q to BVH-order primitive i; (u, v) = the barycentrics of the closest point of a triangle (untouched for a sphere).
 template <typename T, int Leaf>
 __device__ inline T leaf_dist2(const T* prims, uint32_t i, const T (&q)[3], T& u, T& v) {
@@ -133,6 +159,20 @@ __device__ inline void store_stream(V* p, V v) {
     __builtin_nontemporal_store(v, p);
 #else
     *p = v;
+#endif
+}
+
+// A list record is written once and not read again by the launch: one streaming store of 16 bytes (float) or two (double).
+__device__ inline void store_record(bvh_hit3f* out, uint32_t prim, float t, float u, float v) { store_hit_nt(out, prim, t, u, v); }
+__device__ inline void store_record(bvh_hit3d* out, uint32_t prim, double t, double u, double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    d2 a, b;
+    a.x = __longlong_as_double(static_cast<long long>(prim)); a.y = t; b.x = u; b.y = v;
+    __builtin_nontemporal_store(a, reinterpret_cast<d2*>(out));
+    __builtin_nontemporal_store(b, reinterpret_cast<d2*>(out) + 1);
+#else
+    store_hit(out, prim, t, u, v);
 #endif
 }
 

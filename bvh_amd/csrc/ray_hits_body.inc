@@ -1,11 +1,11 @@
 // Per-lane body of the batched all-hits ray query (ray_hits.hip): every BVH-order primitive — a PrecomputedTri or a Sphere — that
 // the UNSHORTENED ray {org, dir, tmin, tmax} crosses, as a count and, optionally, a list of hit records in the ray's segment of a
-// caller-sized buffer. It is the third client of list_walk.inc, next to radius_body.inc and overlap_body.inc: the enter test is the
+// caller-sized buffer. It is a client of list_walk.inc, like radius_body.inc and overlap_body.inc: the enter test is the
 // ray / box slab test of the ray walks (trace_device.h: ray_constants, slab_pair), the hit test their ray / primitive test
 // (ray_prim_test.inc: tri_test.inc, the sphere expressions of trace_body.inc; shared with ray_nearest_body.inc), both against the ray's own [tmin, tmax]: nothing a hit finds shortens
 // the ray, so the list is what the reference's intersect<false, Robust> reports to a leaf_fn that never shortens it.
 // Kept as an include so that tests/cpp/ray_hits_body_host.cpp compiles the very same text for the host (one emulated lane per ray).
-// Expects what point_walk.inc expects.
+// The records leave through point_walk.inc's store_record. Expects what point_walk.inc expects.
 #pragma once
 
 #include "list_walk.inc"
@@ -20,20 +20,6 @@ template <typename T>
 struct RayHitsArgs : ListArgs<T> {             // queries = rays, 8 scalars each; counts = primitives crossed; list_prims is unused
     typename HitOf<T>::Type* list_hits;        // Fill kernels only: the record intersect writes, one per listed primitive
 };
-
-// A list record is written once and not read again by the launch: one streaming store of 16 bytes (float) or two (double).
-__device__ inline void store_record(bvh_hit3f* out, uint32_t prim, float t, float u, float v) { store_hit_nt(out, prim, t, u, v); }
-__device__ inline void store_record(bvh_hit3d* out, uint32_t prim, double t, double u, double v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    d2 a, b;
-    a.x = __longlong_as_double(static_cast<long long>(prim)); a.y = t; b.x = u; b.y = v;
-    __builtin_nontemporal_store(a, reinterpret_cast<d2*>(out));
-    __builtin_nontemporal_store(b, reinterpret_cast<d2*>(out) + 1);
-#else
-    store_hit(out, prim, t, u, v);
-#endif
-}
 
 // One ray, one lane: list_walk (which has the order of the walk and the shape of the output). A child is entered iff the ray's
 // [tmin, tmax] meets its box (bvh.h:177-180 through slab_pair; a NaN bound fails); a primitive matches iff the leaf test of the ray

@@ -4,14 +4,13 @@
 // knn_heap.inc's, keyed by the hit's t in place of a squared distance; the walk is nearest_walk.inc's, keyed by the t at which the ray
 // enters a box — the order of the closest-hit walk of trace_body.inc, both node tests through slab_pair (trace_device.h) — and pruned
 // against the worst of the k candidates held instead of the best hit; the leaf test is all-hits' (ray_prim_test.inc: tri_test.inc, the
-// sphere expressions of trace_body.inc) against the ray's OWN [tmin, tmax], and the records are ray_hits_body.inc's. Only {t, index} is
+// sphere expressions of trace_body.inc) against the ray's OWN [tmin, tmax], and the records are all-hits' (point_walk.inc: store_record). Only {t, index} is
 // kept per candidate: the winners' records are rebuilt at the end by running the leaf test again (a pure function of ray and
 // primitive: the same bits).
 // Kept as an include so that tests/cpp/ray_nearest_body_host.cpp compiles the very same text for the host (one emulated lane per
 // ray). Expects what point_walk.inc expects.
 #pragma once
 
-#include "ray_hits_body.inc"                   // store_record (and, through list_walk.inc, point_walk.inc)
 #include "nearest_walk.inc"
 #include "knn_heap.inc"
 

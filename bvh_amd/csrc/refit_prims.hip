@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) k_max_u32(const uint32_t* v, size_t n, ui
 
 } // namespace
 
-// The largest value in d_prim_ids (one read-back; the caller caches it per tree).
+// The largest value in d_prim_ids (one read-back; largest_prim_id below, its only caller, caches it per tree).
 int max_prim_id_device(const uint32_t* d_prim_ids, size_t prim_count, hipStream_t stream, uint32_t* out) {
     *out = 0;
     if (prim_count == 0) return BVH_AMD_OK;
@@ -76,6 +76,34 @@ int max_prim_id_device(const uint32_t* d_prim_ids, size_t prim_count, hipStream_
     BVH_HIP_TRY(hipStreamSynchronize(stream), BVH_AMD_ERR_HIP);
     return BVH_AMD_OK;
 }
+
+template <typename T>
+int largest_prim_id(const BvhImpl<T>& b, hipStream_t stream, long long* out) {
+    long long largest = b.max_prim_id.load();
+    if (largest < 0) {
+        uint32_t found = 0;
+        if (const int rc = max_prim_id_device(b.d_prim_ids, b.prim_count, stream, &found)) return rc;
+        b.max_prim_id = largest = found;
+    }
+    *out = largest;
+    return BVH_AMD_OK;
+}
+
+template <typename T>
+int source_array_check(const BvhImpl<T>& b, size_t n_src, const char* noun, const std::string& who, hipStream_t stream) {
+    if (!b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, who + ": BVH has no device prim ids");
+    long long largest = 0;
+    if (const int rc = largest_prim_id(b, stream, &largest)) return rc;
+    if (b.prim_count && n_src <= static_cast<size_t>(largest))
+        return fail(BVH_AMD_ERR_ARG, who + ": " + std::to_string(n_src) + " " + noun + " given, but prim_ids refers to primitive " +
+                    std::to_string(largest) + " (the array is indexed by original primitive id)");
+    return BVH_AMD_OK;
+}
+
+template int largest_prim_id<float>(const BvhImpl<float>&, hipStream_t, long long*);
+template int largest_prim_id<double>(const BvhImpl<double>&, hipStream_t, long long*);
+template int source_array_check<float>(const BvhImpl<float>&, size_t, const char*, const std::string&, hipStream_t);
+template int source_array_check<double>(const BvhImpl<double>&, size_t, const char*, const std::string&, hipStream_t);
 
 // Leaf boxes from `d_src` (src_kind: REFIT_BOXES3 / REFIT_BOXES2 / REFIT_TRIS), inner boxes bottom-up, both representations in place.
 // Asynchronous on `stream`. (dimension-independent above the leaves: z stays (+0, +0) in 2D)

@@ -61,16 +61,7 @@ int launch_region(const BvhImpl<T>& b, int leaf_kind, const T* d_prims, size_t n
     const char* fault = list_output_fault(d_counts, d_offsets, d_list_prims, d_list_inside);
     if (!fault && !aligned) fault = "device pointers must be aligned (primitives and planes to their scalar, offsets and counters 8 bytes, counts and list prims 4)";
     if (const int rc = point_query_check(b, n, walk_flags, d_prims && d_planes, fault, who); rc || n == 0) return rc;
-    if (!b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH has no device prim ids");
-    long long largest = b.max_prim_id.load();
-    if (largest < 0) {                                        // one read-back per layout, shared with overlap_* / refit_boxes / refit_tris
-        uint32_t found = 0;
-        if (const int rc = max_prim_id_device(b.d_prim_ids, b.prim_count, stream, &found)) return rc;
-        b.max_prim_id = largest = found;
-    }
-    if (b.prim_count && n_prims <= static_cast<size_t>(largest))
-        return fail(BVH_AMD_ERR_ARG, std::string(who) + ": " + std::to_string(n_prims) + " primitives given, but prim_ids refers to primitive " +
-                    std::to_string(largest) + " (the array is indexed by original primitive id)");
+    if (const int rc = source_array_check(b, n_prims, "primitives", who, stream)) return rc;
     return point_query_run<T>(b, d_prims, d_planes, n, walk_flags | BVH_AMD_RAY_UNSORTED, d_counters, sizeof(uint32_t), kBlock, kPointSortMin, kPointKeyBits, who,
                               stream, [&](const PointArgs<T>& args, T*) {
         const RegionArgs<T> a{{args, d_counts, reinterpret_cast<const unsigned long long*>(d_offsets), d_list_prims}, b.d_prim_ids, d_list_inside,

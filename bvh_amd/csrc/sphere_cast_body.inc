@@ -2,13 +2,13 @@
 // t in [tmin, tmax], and the smallest t at which it touches the scene: dist(c(t), primitive) <= r (closed), over solid triangles
 // (PrecomputedTri) or solid spheres. It is the third client of nearest_walk.inc, next to closest_body.inc and ray_nearest_body.inc:
 // the key of a box is the t at which the ray enters the box GROWN by r on every side (slab_pair, trace_device.h), the limit is the
-// best contact so far, and the leaf test is the sweep test below. Kept as an include so that tests/cpp/sphere_cast_body_host.cpp
-// compiles the very same text for the host (one emulated lane per query). Expects what point_walk.inc expects, and store_record.
+// best contact so far, and the leaf test is the sweep test below; the LDS tier of the stack is closest-point's (nearest_walk.inc:
+// kClosestLds) and the record leaves through point_walk.inc's store_record. Kept as an include so that
+// tests/cpp/sphere_cast_body_host.cpp compiles the very same text for the host (one emulated lane per query). Expects what
+// point_walk.inc expects.
 #pragma once
 
-#include "ray_hits_body.inc"                   // store_record (and, through list_walk.inc, point_walk.inc)
 #include "nearest_walk.inc"
-#include "closest_body.inc"                    // kClosestLds: the LDS tier of the stack is closest-point's
 
 namespace bvh_amd {
 

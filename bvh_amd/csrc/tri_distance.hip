@@ -3,7 +3,7 @@
 // closest, as one hit record {prim, t, u, v} and, optionally, the barycentrics of the closest point on the query triangle. The
 // primitives' triangles are the caller's array indexed by original primitive id, the one bvh3X_intersect_tris and bvh3X_refit_tris
 // take, read through the tree's prim ids. The per-lane walk and the pair distance are tri_distance_body.inc (shared with the host
-// test harness, tests/cpp/tri_distance_body_host.cpp) over nearest_walk.inc and the sign-only pair test of tri_intersect_body.inc,
+// test harness, tests/cpp/tri_distance_body_host.cpp) over nearest_walk.inc and the sign-only pair test of tri_pair.inc,
 // which decides distance 0; the launch path is point_query.h's; this file holds the kernel and what is specific to the query.
 //
 // MI355X mapping (closest.hip's, with a box / box key and a triangle pair behind the primitive's box test):
@@ -58,16 +58,7 @@ int launch_tri_distance(const BvhImpl<T>& b, const T* d_tris9, size_t n_tris, co
                                          who);
         rc || n == 0)
         return rc;
-    if (!b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH has no device prim ids");
-    long long largest = b.max_prim_id.load();
-    if (largest < 0) {                                        // one read-back per layout, shared with intersect_tris / overlap_* / refit_*
-        uint32_t found = 0;
-        if (const int rc = max_prim_id_device(b.d_prim_ids, b.prim_count, stream, &found)) return rc;
-        b.max_prim_id = largest = found;
-    }
-    if (b.prim_count && n_tris <= static_cast<size_t>(largest))
-        return fail(BVH_AMD_ERR_ARG, std::string(who) + ": " + std::to_string(n_tris) + " triangles given, but prim_ids refers to primitive " +
-                    std::to_string(largest) + " (the array is indexed by original primitive id)");
+    if (const int rc = source_array_check(b, n_tris, "triangles", who, stream)) return rc;
     // (kPointSortMin: the threshold measured for closest-point queries; not measured for this kind. tools/bench_tri_distance.py times
     //  SORTED against UNSORTED.)
     return point_query_run<T, kQueryTris>(b, d_tris9, d_queries9, n, flags, d_counters, sizeof(uint32_t) + sizeof(T), kBlock, kPointSortMin, kPointKeyBits, who,

@@ -4,13 +4,13 @@
 // caller's array of 9 scalars indexed by ORIGINAL primitive id (tri_intersect_body.inc: the triangle of BVH-order primitive i is
 // tris[tri_ids[i]]). It is the fourth client of nearest_walk.inc, next to closest_body.inc, ray_nearest_body.inc and
 // sphere_cast_body.inc: the key of a box is its squared distance to the query triangle's box, the limit is the best squared distance
-// so far, and the leaf test is the pair distance below. Kept as an include so that tests/cpp/tri_distance_body_host.cpp compiles
-// the very same text for the host (one emulated lane per query). Expects what point_walk.inc expects.
+// so far, and the leaf test is the pair distance below; the LDS tier of the stack is closest-point's (nearest_walk.inc:
+// kClosestLds). Kept as an include so that tests/cpp/tri_distance_body_host.cpp compiles the very same text for the host (one
+// emulated lane per query). Expects what point_walk.inc expects.
 #pragma once
 
-#include "tri_intersect_body.inc"              // load_tri9, tri_box, tri_normal, normal_usable, tri_pair_intersects
+#include "tri_pair.inc"                        // load_tri9, tri_box, tri_normal, normal_usable, tri_pair_intersects
 #include "nearest_walk.inc"
-#include "closest_body.inc"                    // kClosestLds: the LDS tier of the stack is closest-point's
 
 namespace bvh_amd {
 
@@ -27,7 +27,7 @@ struct TriDistanceArgs : PointArgs<T> {        // prims = the triangles, n_tris 
 };
 
 // (Vectors are structs of three named scalars and the loops below ROTATE them instead of indexing arrays of vertices: a lane's
-//  array indexed by a loop counter becomes scratch wherever the compiler keeps the loop; tri_intersect_body.inc has the same note.)
+//  array indexed by a loop counter becomes scratch wherever the compiler keeps the loop; tri_pair.inc has the same note.)
 template <typename T>
 struct Td3 { T x, y, z; };
 
@@ -132,7 +132,7 @@ __device__ inline void td_edges_to_face(Td3<T> a, Td3<T> b, Td3<T> c, const TdFa
 template <typename T>
 struct TdQuery {
     T raw[9], lo[3], hi[3], n[3];              // the vertices as given, their box, (p1 - p0) x (p2 - p0)
-    bool usable;                               // normal_usable(n): the pair test of tri_intersect_body.inc applies
+    bool usable;                               // normal_usable(n): the pair test of tri_pair.inc applies
     TdFace<T> face;                            // in the local frame (origin p0): o = 0, ab = p1 - p0, ac = p2 - p0
     T e1, ie0, ie1, ie2;                       // |p2 - p1|^2 and td_inv of the three squared edge lengths (edge 0: abab, edge 2: acac)
 };

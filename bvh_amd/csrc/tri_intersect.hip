@@ -3,7 +3,7 @@
 // narrow phase of a collision test, inside the walk of the broad phase). The primitives' triangles are the caller's array indexed by
 // original primitive id, the one bvh3X_refit_tris takes, read through the tree's prim ids. The per-lane body is
 // tri_intersect_body.inc (shared with the host test harness, tests/cpp/tri_intersect_body_host.cpp): the query triangle and the
-// sign-only pair test, handed to the walk overlap.hip and radius.hip use, list_walk.inc (stack, descent, counts, segments), over
+// sign-only pair test (tri_pair.inc), handed to the walk overlap.hip and radius.hip use, list_walk.inc (stack, descent, counts, segments), over
 // point_walk.inc (stack tiers, streaming stores); the launch path is point_query.h's.
 //
 // MI355X mapping (overlap.hip's, with a triangle test behind the primitive's box test):
@@ -59,16 +59,7 @@ int launch_tri_intersect(const BvhImpl<T>& b, bool self, const T* d_tris9, size_
     const char* fault = list_output_fault(d_counts, d_offsets, d_list_prims, nullptr);
     if (!fault && !aligned) fault = "device pointers must be aligned (triangles and queries to their scalar, offsets and counters 8 bytes, counts and list prims 4)";
     if (const int rc = point_query_check(b, n, walk_flags, d_tris9 && (self || d_queries9), fault, who); rc || n == 0) return rc;
-    if (!b.d_prim_ids) return fail(BVH_AMD_ERR_ARG, std::string(who) + ": BVH has no device prim ids");
-    long long largest = b.max_prim_id.load();
-    if (largest < 0) {                                        // one read-back per layout, shared with overlap_* / refit_boxes / refit_tris
-        uint32_t found = 0;
-        if (const int rc = max_prim_id_device(b.d_prim_ids, b.prim_count, stream, &found)) return rc;
-        b.max_prim_id = largest = found;
-    }
-    if (b.prim_count && n_tris <= static_cast<size_t>(largest))
-        return fail(BVH_AMD_ERR_ARG, std::string(who) + ": " + std::to_string(n_tris) + " triangles given, but prim_ids refers to primitive " +
-                    std::to_string(largest) + " (the array is indexed by original primitive id)");
+    if (const int rc = source_array_check(b, n_tris, "triangles", who, stream)) return rc;
     const unsigned run_flags = self ? walk_flags | BVH_AMD_RAY_UNSORTED : walk_flags;
     const uint32_t skip_shared = (flags & BVH_AMD_TRI_SKIP_SHARED) ? 1u : 0u;
     // (kPointSortMin: the threshold measured for closest-point queries; not measured for this kind, which takes it as radius and

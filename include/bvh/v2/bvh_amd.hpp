@@ -289,119 +289,65 @@ struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
 inline void check(int rc, const char* what) { if (rc != 0) throw Error(std::string(what) + ": " + bvh_amd_last_error()); }
 
 template <typename T, size_t N = 3> struct Api;
-template <> struct Api<float, 3> {
-    using Handle = bvh3f; using CHit = bvh_hit3f;
-    static Handle* build(bvh_thread_pool* p, const void* bb, const void* cc, size_t n, const bvh_build_config* c) { return bvh3f_build(p, static_cast<const bvh_bbox3f*>(bb), static_cast<const bvh_vec3f*>(cc), n, c); }
-    static Handle* build_device(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, bvh_amd_builder b) { return bvh3f_build_device(static_cast<const float*>(d_bb), static_cast<const float*>(d_cc), n, c, b, nullptr); }
-    static Handle* build_sah(bvh_thread_pool* p, const void* bb, const void* cc, size_t n, const bvh_build_config* c, const bvh_amd_sah_config* h) { return bvh3f_build_sah(p, static_cast<const bvh_bbox3f*>(bb), static_cast<const bvh_vec3f*>(cc), n, c, h); }
-    static Handle* build_device_sah(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, bvh_amd_builder b, const bvh_amd_sah_config* h) { return bvh3f_build_device_sah(static_cast<const float*>(d_bb), static_cast<const float*>(d_cc), n, c, b, h, nullptr); }
-    static Handle* build_device_binned(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, const bvh_amd_sah_config* h, size_t bins) { return bvh3f_build_device_binned(static_cast<const float*>(d_bb), static_cast<const float*>(d_cc), n, c, h, bins, nullptr); }
-    static Handle* build_minitree(const void* d_bb, const void* d_cc, size_t n, const bvh_amd_minitree_config* c) { return bvh3f_build_minitree_device(static_cast<const float*>(d_bb), static_cast<const float*>(d_cc), n, c, nullptr); }
-    static Handle* from_nodes(const void* nodes, size_t nn, const size_t* ids, size_t np) { return bvh3f_from_nodes(nodes, nn, ids, np); }
-    static void destroy(Handle* h) { bvh3f_destroy(h); }
-    static size_t node_count(const Handle* h) { return bvh3f_get_node_count(h); }
-    static size_t prim_count(const Handle* h) { return bvh3f_get_prim_count(h); }
-    static void copy_nodes(const Handle* h, void* out) { bvh3f_copy_nodes(h, out); }
-    static void copy_prim_ids(const Handle* h, size_t* out) { bvh3f_copy_prim_ids(h, out); }
-    static Handle* extract(Handle* h, size_t root_id) { return bvh3f_extract(h, root_id); }
-    static void optimize(Handle* h) { bvh3f_optimize(nullptr, h); }
-    static int optimize_config(Handle* h, const bvh_amd_optimize_config* c) { return bvh3f_optimize_config(h, c); }
-    static void refit(Handle* h) { bvh3f_refit(h); }
-    static int refit_boxes(Handle* h, const void* d_bb, size_t n) { return bvh3f_refit_boxes(h, static_cast<const float*>(d_bb), n, nullptr); }
-    static int refit_tris(Handle* h, const void* d_t9, size_t n, void* d_out12) { return bvh3f_refit_tris(h, static_cast<const float*>(d_t9), n, static_cast<float*>(d_out12), nullptr); }
-    static int traversal_cost(Handle* h, double* out) { return bvh3f_traversal_cost(h, out, nullptr); }
-    static const uint32_t* device_prim_ids(const Handle* h) { return bvh3f_device_prim_ids(h); }
-    static Handle* broadcast(bvh_amd_comm* c, int root, Handle* h, const void* p, size_t bytes, void** p_out, size_t* bytes_out) { return bvh3f_broadcast(c, root, h, p, bytes, p_out, bytes_out, nullptr); }
-    static int replicate(Handle* h, const void* p, size_t bytes, int n, const int* devs, Handle** out, void** p_out) { return bvh3f_replicate(h, p, bytes, n, devs, out, p_out); }
-    static int precompute(const void* t9, const uint32_t* perm, size_t n, void* out) { return bvh_amd_precompute_tris3f(static_cast<const float*>(t9), perm, n, static_cast<float*>(out), nullptr); }
-    static int trace_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3f_intersect_rays_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int trace_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3f_intersect_rays_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int closest_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3f_closest_points_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3f_closest_points_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
-    static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3f_radius_search_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, f, counts, offsets, list, static_cast<float*>(dist), nullptr, nullptr); }
-    static int all_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3f_intersect_rays_all_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, counts, offsets, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3f_intersect_rays_all_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, f, counts, offsets, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int nearest_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3f_intersect_rays_nearest_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, k, f, static_cast<bvh_hit3f*>(hits), counts, nullptr, nullptr); }
-    static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3f_intersect_rays_nearest_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, k, f, static_cast<bvh_hit3f*>(hits), counts, nullptr, nullptr); }
-    static int sphere_cast_tri(const Handle* h, const void* prims, const void* rays, size_t n, float radius, const float* radii, unsigned f, void* hits) { return bvh3f_sphere_cast_tri(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, radius, radii, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int sphere_cast_sphere(const Handle* h, const void* prims, const void* rays, size_t n, float radius, const float* radii, unsigned f, void* hits) { return bvh3f_sphere_cast_sphere(h, static_cast<const float*>(prims), static_cast<const bvh_ray3f*>(rays), n, radius, radii, f, static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int tri_distance(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, float max_distance, const float* max_distances, unsigned f, void* hits, float* query_uv) { return bvh3f_tri_distance(h, static_cast<const float*>(t9), nt, static_cast<const float*>(queries), n, max_distance, max_distances, f, static_cast<bvh_hit3f*>(hits), query_uv, nullptr, nullptr); }
-    static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_tri(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
-    static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3f_knn_sphere(h, static_cast<const float*>(prims), static_cast<const float*>(queries), n, k, f, out_prims, static_cast<float*>(out_dist), counts, nullptr, nullptr); }
-    static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh3f_winding_prepare(h, static_cast<const float*>(tris), static_cast<float*>(moments), rows, nullptr); }
-    static int winding_numbers(const Handle* h, const void* tris, const void* moments, size_t rows, const void* queries, size_t n, double beta, unsigned f, void* w, void* hits) { return bvh3f_winding_numbers(h, static_cast<const float*>(tris), static_cast<const float*>(moments), rows, static_cast<const float*>(queries), n, beta, f, static_cast<float*>(w), static_cast<bvh_hit3f*>(hits), nullptr, nullptr); }
-    static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_boxes(h, static_cast<const float*>(bb), nb, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
-    static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_overlap_self(h, static_cast<const float*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
-    static int region_tris(const Handle* h, const void* t9, size_t nt, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh3f_region_tris(h, static_cast<const float*>(t9), nt, static_cast<const float*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); }
-    static int region_spheres(const Handle* h, const void* s4, size_t ns, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh3f_region_spheres(h, static_cast<const float*>(s4), ns, static_cast<const float*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); }
-    static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_intersect_tris(h, static_cast<const float*>(t9), nt, static_cast<const float*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
-    static int intersect_tris_self(const Handle* h, const void* t9, size_t nt, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3f_intersect_tris_self(h, static_cast<const float*>(t9), nt, f, counts, offsets, list, nullptr, nullptr); }
-    using CGeometry = bvh_amd_geometry3f;
-    static int instance_prepare(const CGeometry* g, size_t ng, const void* m, const uint32_t* gid, size_t n, void* w, void* bb, void* cc) { return bvh3f_instance_prepare(g, ng, static_cast<const float*>(m), gid, n, static_cast<float*>(w), static_cast<float*>(bb), static_cast<float*>(cc), nullptr); }
-    static int trace_instanced(const Handle* top, const CGeometry* g, size_t ng, const void* w, const uint32_t* gid, size_t n, const void* rays, size_t nr, unsigned f, void* hits, uint32_t* inst) { return bvh3f_intersect_rays_instanced(top, g, ng, static_cast<const float*>(w), gid, n, static_cast<const bvh_ray3f*>(rays), nr, f, static_cast<bvh_hit3f*>(hits), inst, nullptr, nullptr); }
-    static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, float*, size_t, size_t), void (*inner)(void*, size_t)) {
-        const bvh_amd_ray_visitorf v{ user, leaf, inner };
-        return bvh3f_intersect_ray_visit(h, static_cast<const bvh_ray3f*>(ray), start, f, &v);
-    }
+#define BVH_AMD_API_3D(T, S)                                                                                                              \
+template <> struct Api<T, 3> {                                                                                                            \
+    using Handle = bvh##S; using CHit = bvh_hit##S;                                                                                       \
+    static Handle* build(bvh_thread_pool* p, const void* bb, const void* cc, size_t n, const bvh_build_config* c) { return bvh##S##_build(p, static_cast<const bvh_bbox##S*>(bb), static_cast<const bvh_vec##S*>(cc), n, c); } \
+    static Handle* build_device(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, bvh_amd_builder b) { return bvh##S##_build_device(static_cast<const T*>(d_bb), static_cast<const T*>(d_cc), n, c, b, nullptr); } \
+    static Handle* build_sah(bvh_thread_pool* p, const void* bb, const void* cc, size_t n, const bvh_build_config* c, const bvh_amd_sah_config* h) { return bvh##S##_build_sah(p, static_cast<const bvh_bbox##S*>(bb), static_cast<const bvh_vec##S*>(cc), n, c, h); } \
+    static Handle* build_device_sah(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, bvh_amd_builder b, const bvh_amd_sah_config* h) { return bvh##S##_build_device_sah(static_cast<const T*>(d_bb), static_cast<const T*>(d_cc), n, c, b, h, nullptr); } \
+    static Handle* build_device_binned(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, const bvh_amd_sah_config* h, size_t bins) { return bvh##S##_build_device_binned(static_cast<const T*>(d_bb), static_cast<const T*>(d_cc), n, c, h, bins, nullptr); } \
+    static Handle* build_minitree(const void* d_bb, const void* d_cc, size_t n, const bvh_amd_minitree_config* c) { return bvh##S##_build_minitree_device(static_cast<const T*>(d_bb), static_cast<const T*>(d_cc), n, c, nullptr); } \
+    static Handle* from_nodes(const void* nodes, size_t nn, const size_t* ids, size_t np) { return bvh##S##_from_nodes(nodes, nn, ids, np); } \
+    static void destroy(Handle* h) { bvh##S##_destroy(h); }                                                                               \
+    static size_t node_count(const Handle* h) { return bvh##S##_get_node_count(h); }                                                      \
+    static size_t prim_count(const Handle* h) { return bvh##S##_get_prim_count(h); }                                                      \
+    static void copy_nodes(const Handle* h, void* out) { bvh##S##_copy_nodes(h, out); }                                                   \
+    static void copy_prim_ids(const Handle* h, size_t* out) { bvh##S##_copy_prim_ids(h, out); }                                           \
+    static Handle* extract(Handle* h, size_t root_id) { return bvh##S##_extract(h, root_id); }                                            \
+    static void optimize(Handle* h) { bvh##S##_optimize(nullptr, h); }                                                                    \
+    static int optimize_config(Handle* h, const bvh_amd_optimize_config* c) { return bvh##S##_optimize_config(h, c); }                    \
+    static void refit(Handle* h) { bvh##S##_refit(h); }                                                                                   \
+    static int refit_boxes(Handle* h, const void* d_bb, size_t n) { return bvh##S##_refit_boxes(h, static_cast<const T*>(d_bb), n, nullptr); } \
+    static int refit_tris(Handle* h, const void* d_t9, size_t n, void* d_out12) { return bvh##S##_refit_tris(h, static_cast<const T*>(d_t9), n, static_cast<T*>(d_out12), nullptr); } \
+    static int traversal_cost(Handle* h, double* out) { return bvh##S##_traversal_cost(h, out, nullptr); }                                \
+    static const uint32_t* device_prim_ids(const Handle* h) { return bvh##S##_device_prim_ids(h); }                                       \
+    static Handle* broadcast(bvh_amd_comm* c, int root, Handle* h, const void* p, size_t bytes, void** p_out, size_t* bytes_out) { return bvh##S##_broadcast(c, root, h, p, bytes, p_out, bytes_out, nullptr); } \
+    static int replicate(Handle* h, const void* p, size_t bytes, int n, const int* devs, Handle** out, void** p_out) { return bvh##S##_replicate(h, p, bytes, n, devs, out, p_out); } \
+    static int precompute(const void* t9, const uint32_t* perm, size_t n, void* out) { return bvh_amd_precompute_tris##S(static_cast<const T*>(t9), perm, n, static_cast<T*>(out), nullptr); } \
+    static int trace_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh##S##_intersect_rays_tri(h, static_cast<const T*>(prims), static_cast<const bvh_ray##S*>(rays), n, f, static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int trace_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh##S##_intersect_rays_sphere(h, static_cast<const T*>(prims), static_cast<const bvh_ray##S*>(rays), n, f, static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int closest_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh##S##_closest_points_tri(h, static_cast<const T*>(prims), static_cast<const T*>(queries), n, f, static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh##S##_closest_points_sphere(h, static_cast<const T*>(prims), static_cast<const T*>(queries), n, f, static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh##S##_radius_search_tri(h, static_cast<const T*>(prims), static_cast<const T*>(queries), n, f, counts, offsets, list, static_cast<T*>(dist), nullptr, nullptr); } \
+    static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh##S##_radius_search_sphere(h, static_cast<const T*>(prims), static_cast<const T*>(queries), n, f, counts, offsets, list, static_cast<T*>(dist), nullptr, nullptr); } \
+    static int all_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh##S##_intersect_rays_all_tri(h, static_cast<const T*>(prims), static_cast<const bvh_ray##S*>(rays), n, f, counts, offsets, static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh##S##_intersect_rays_all_sphere(h, static_cast<const T*>(prims), static_cast<const bvh_ray##S*>(rays), n, f, counts, offsets, static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int nearest_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh##S##_intersect_rays_nearest_tri(h, static_cast<const T*>(prims), static_cast<const bvh_ray##S*>(rays), n, k, f, static_cast<CHit*>(hits), counts, nullptr, nullptr); } \
+    static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh##S##_intersect_rays_nearest_sphere(h, static_cast<const T*>(prims), static_cast<const bvh_ray##S*>(rays), n, k, f, static_cast<CHit*>(hits), counts, nullptr, nullptr); } \
+    static int sphere_cast_tri(const Handle* h, const void* prims, const void* rays, size_t n, T radius, const T* radii, unsigned f, void* hits) { return bvh##S##_sphere_cast_tri(h, static_cast<const T*>(prims), static_cast<const bvh_ray##S*>(rays), n, radius, radii, f, static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int sphere_cast_sphere(const Handle* h, const void* prims, const void* rays, size_t n, T radius, const T* radii, unsigned f, void* hits) { return bvh##S##_sphere_cast_sphere(h, static_cast<const T*>(prims), static_cast<const bvh_ray##S*>(rays), n, radius, radii, f, static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int tri_distance(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, T max_distance, const T* max_distances, unsigned f, void* hits, T* query_uv) { return bvh##S##_tri_distance(h, static_cast<const T*>(t9), nt, static_cast<const T*>(queries), n, max_distance, max_distances, f, static_cast<CHit*>(hits), query_uv, nullptr, nullptr); } \
+    static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh##S##_knn_tri(h, static_cast<const T*>(prims), static_cast<const T*>(queries), n, k, f, out_prims, static_cast<T*>(out_dist), counts, nullptr, nullptr); } \
+    static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh##S##_knn_sphere(h, static_cast<const T*>(prims), static_cast<const T*>(queries), n, k, f, out_prims, static_cast<T*>(out_dist), counts, nullptr, nullptr); } \
+    static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh##S##_winding_prepare(h, static_cast<const T*>(tris), static_cast<T*>(moments), rows, nullptr); } \
+    static int winding_numbers(const Handle* h, const void* tris, const void* moments, size_t rows, const void* queries, size_t n, double beta, unsigned f, void* w, void* hits) { return bvh##S##_winding_numbers(h, static_cast<const T*>(tris), static_cast<const T*>(moments), rows, static_cast<const T*>(queries), n, beta, f, static_cast<T*>(w), static_cast<CHit*>(hits), nullptr, nullptr); } \
+    static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh##S##_overlap_boxes(h, static_cast<const T*>(bb), nb, static_cast<const T*>(queries), n, f, counts, offsets, list, nullptr, nullptr); } \
+    static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh##S##_overlap_self(h, static_cast<const T*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); } \
+    static int region_tris(const Handle* h, const void* t9, size_t nt, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh##S##_region_tris(h, static_cast<const T*>(t9), nt, static_cast<const T*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); } \
+    static int region_spheres(const Handle* h, const void* s4, size_t ns, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh##S##_region_spheres(h, static_cast<const T*>(s4), ns, static_cast<const T*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); } \
+    static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh##S##_intersect_tris(h, static_cast<const T*>(t9), nt, static_cast<const T*>(queries), n, f, counts, offsets, list, nullptr, nullptr); } \
+    static int intersect_tris_self(const Handle* h, const void* t9, size_t nt, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh##S##_intersect_tris_self(h, static_cast<const T*>(t9), nt, f, counts, offsets, list, nullptr, nullptr); } \
+    using CGeometry = bvh_amd_geometry##S;                                                                                                \
+    static int instance_prepare(const CGeometry* g, size_t ng, const void* m, const uint32_t* gid, size_t n, void* w, void* bb, void* cc) { return bvh##S##_instance_prepare(g, ng, static_cast<const T*>(m), gid, n, static_cast<T*>(w), static_cast<T*>(bb), static_cast<T*>(cc), nullptr); } \
+    static int trace_instanced(const Handle* top, const CGeometry* g, size_t ng, const void* w, const uint32_t* gid, size_t n, const void* rays, size_t nr, unsigned f, void* hits, uint32_t* inst) { return bvh##S##_intersect_rays_instanced(top, g, ng, static_cast<const T*>(w), gid, n, static_cast<const bvh_ray##S*>(rays), nr, f, static_cast<CHit*>(hits), inst, nullptr, nullptr); } \
+    static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, T*, size_t, size_t), void (*inner)(void*, size_t)) { \
+        const std::conditional_t<std::is_same_v<T, float>, bvh_amd_ray_visitorf, bvh_amd_ray_visitord> v{ user, leaf, inner };           \
+        return bvh##S##_intersect_ray_visit(h, static_cast<const bvh_ray##S*>(ray), start, f, &v); }                                      \
 };
-template <> struct Api<double, 3> {
-    using Handle = bvh3d; using CHit = bvh_hit3d;
-    static Handle* build(bvh_thread_pool* p, const void* bb, const void* cc, size_t n, const bvh_build_config* c) { return bvh3d_build(p, static_cast<const bvh_bbox3d*>(bb), static_cast<const bvh_vec3d*>(cc), n, c); }
-    static Handle* build_device(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, bvh_amd_builder b) { return bvh3d_build_device(static_cast<const double*>(d_bb), static_cast<const double*>(d_cc), n, c, b, nullptr); }
-    static Handle* build_sah(bvh_thread_pool* p, const void* bb, const void* cc, size_t n, const bvh_build_config* c, const bvh_amd_sah_config* h) { return bvh3d_build_sah(p, static_cast<const bvh_bbox3d*>(bb), static_cast<const bvh_vec3d*>(cc), n, c, h); }
-    static Handle* build_device_sah(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, bvh_amd_builder b, const bvh_amd_sah_config* h) { return bvh3d_build_device_sah(static_cast<const double*>(d_bb), static_cast<const double*>(d_cc), n, c, b, h, nullptr); }
-    static Handle* build_device_binned(const void* d_bb, const void* d_cc, size_t n, const bvh_build_config* c, const bvh_amd_sah_config* h, size_t bins) { return bvh3d_build_device_binned(static_cast<const double*>(d_bb), static_cast<const double*>(d_cc), n, c, h, bins, nullptr); }
-    static Handle* build_minitree(const void* d_bb, const void* d_cc, size_t n, const bvh_amd_minitree_config* c) { return bvh3d_build_minitree_device(static_cast<const double*>(d_bb), static_cast<const double*>(d_cc), n, c, nullptr); }
-    static Handle* from_nodes(const void* nodes, size_t nn, const size_t* ids, size_t np) { return bvh3d_from_nodes(nodes, nn, ids, np); }
-    static void destroy(Handle* h) { bvh3d_destroy(h); }
-    static size_t node_count(const Handle* h) { return bvh3d_get_node_count(h); }
-    static size_t prim_count(const Handle* h) { return bvh3d_get_prim_count(h); }
-    static void copy_nodes(const Handle* h, void* out) { bvh3d_copy_nodes(h, out); }
-    static void copy_prim_ids(const Handle* h, size_t* out) { bvh3d_copy_prim_ids(h, out); }
-    static Handle* extract(Handle* h, size_t root_id) { return bvh3d_extract(h, root_id); }
-    static void optimize(Handle* h) { bvh3d_optimize(nullptr, h); }
-    static int optimize_config(Handle* h, const bvh_amd_optimize_config* c) { return bvh3d_optimize_config(h, c); }
-    static void refit(Handle* h) { bvh3d_refit(h); }
-    static int refit_boxes(Handle* h, const void* d_bb, size_t n) { return bvh3d_refit_boxes(h, static_cast<const double*>(d_bb), n, nullptr); }
-    static int refit_tris(Handle* h, const void* d_t9, size_t n, void* d_out12) { return bvh3d_refit_tris(h, static_cast<const double*>(d_t9), n, static_cast<double*>(d_out12), nullptr); }
-    static int traversal_cost(Handle* h, double* out) { return bvh3d_traversal_cost(h, out, nullptr); }
-    static const uint32_t* device_prim_ids(const Handle* h) { return bvh3d_device_prim_ids(h); }
-    static Handle* broadcast(bvh_amd_comm* c, int root, Handle* h, const void* p, size_t bytes, void** p_out, size_t* bytes_out) { return bvh3d_broadcast(c, root, h, p, bytes, p_out, bytes_out, nullptr); }
-    static int replicate(Handle* h, const void* p, size_t bytes, int n, const int* devs, Handle** out, void** p_out) { return bvh3d_replicate(h, p, bytes, n, devs, out, p_out); }
-    static int precompute(const void* t9, const uint32_t* perm, size_t n, void* out) { return bvh_amd_precompute_tris3d(static_cast<const double*>(t9), perm, n, static_cast<double*>(out), nullptr); }
-    static int trace_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3d_intersect_rays_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int trace_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, void* hits) { return bvh3d_intersect_rays_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int closest_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3d_closest_points_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int closest_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, void* hits) { return bvh3d_closest_points_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int radius_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
-    static int radius_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, void* dist) { return bvh3d_radius_search_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, f, counts, offsets, list, static_cast<double*>(dist), nullptr, nullptr); }
-    static int all_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3d_intersect_rays_all_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, counts, offsets, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int all_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, void* hits) { return bvh3d_intersect_rays_all_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, f, counts, offsets, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int nearest_hits_tri(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3d_intersect_rays_nearest_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, k, f, static_cast<bvh_hit3d*>(hits), counts, nullptr, nullptr); }
-    static int nearest_hits_sphere(const Handle* h, const void* prims, const void* rays, size_t n, unsigned k, unsigned f, void* hits, uint32_t* counts) { return bvh3d_intersect_rays_nearest_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, k, f, static_cast<bvh_hit3d*>(hits), counts, nullptr, nullptr); }
-    static int sphere_cast_tri(const Handle* h, const void* prims, const void* rays, size_t n, double radius, const double* radii, unsigned f, void* hits) { return bvh3d_sphere_cast_tri(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, radius, radii, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int sphere_cast_sphere(const Handle* h, const void* prims, const void* rays, size_t n, double radius, const double* radii, unsigned f, void* hits) { return bvh3d_sphere_cast_sphere(h, static_cast<const double*>(prims), static_cast<const bvh_ray3d*>(rays), n, radius, radii, f, static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int tri_distance(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, double max_distance, const double* max_distances, unsigned f, void* hits, double* query_uv) { return bvh3d_tri_distance(h, static_cast<const double*>(t9), nt, static_cast<const double*>(queries), n, max_distance, max_distances, f, static_cast<bvh_hit3d*>(hits), query_uv, nullptr, nullptr); }
-    static int knn_tri(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_tri(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
-    static int knn_sphere(const Handle* h, const void* prims, const void* queries, size_t n, unsigned k, unsigned f, uint32_t* out_prims, void* out_dist, uint32_t* counts) { return bvh3d_knn_sphere(h, static_cast<const double*>(prims), static_cast<const double*>(queries), n, k, f, out_prims, static_cast<double*>(out_dist), counts, nullptr, nullptr); }
-    static int winding_prepare(const Handle* h, const void* tris, void* moments, size_t rows) { return bvh3d_winding_prepare(h, static_cast<const double*>(tris), static_cast<double*>(moments), rows, nullptr); }
-    static int winding_numbers(const Handle* h, const void* tris, const void* moments, size_t rows, const void* queries, size_t n, double beta, unsigned f, void* w, void* hits) { return bvh3d_winding_numbers(h, static_cast<const double*>(tris), static_cast<const double*>(moments), rows, static_cast<const double*>(queries), n, beta, f, static_cast<double*>(w), static_cast<bvh_hit3d*>(hits), nullptr, nullptr); }
-    static int overlap_boxes(const Handle* h, const void* bb, size_t nb, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_boxes(h, static_cast<const double*>(bb), nb, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
-    static int overlap_self(const Handle* h, const void* bb, size_t nb, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_overlap_self(h, static_cast<const double*>(bb), nb, f, counts, offsets, list, nullptr, nullptr); }
-    static int region_tris(const Handle* h, const void* t9, size_t nt, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh3d_region_tris(h, static_cast<const double*>(t9), nt, static_cast<const double*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); }
-    static int region_spheres(const Handle* h, const void* s4, size_t ns, const void* planes, size_t m, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list, uint8_t* inside) { return bvh3d_region_spheres(h, static_cast<const double*>(s4), ns, static_cast<const double*>(planes), m, n, f, counts, offsets, list, inside, nullptr, nullptr); }
-    static int intersect_tris(const Handle* h, const void* t9, size_t nt, const void* queries, size_t n, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_intersect_tris(h, static_cast<const double*>(t9), nt, static_cast<const double*>(queries), n, f, counts, offsets, list, nullptr, nullptr); }
-    static int intersect_tris_self(const Handle* h, const void* t9, size_t nt, unsigned f, uint32_t* counts, const uint64_t* offsets, uint32_t* list) { return bvh3d_intersect_tris_self(h, static_cast<const double*>(t9), nt, f, counts, offsets, list, nullptr, nullptr); }
-    using CGeometry = bvh_amd_geometry3d;
-    static int instance_prepare(const CGeometry* g, size_t ng, const void* m, const uint32_t* gid, size_t n, void* w, void* bb, void* cc) { return bvh3d_instance_prepare(g, ng, static_cast<const double*>(m), gid, n, static_cast<double*>(w), static_cast<double*>(bb), static_cast<double*>(cc), nullptr); }
-    static int trace_instanced(const Handle* top, const CGeometry* g, size_t ng, const void* w, const uint32_t* gid, size_t n, const void* rays, size_t nr, unsigned f, void* hits, uint32_t* inst) { return bvh3d_intersect_rays_instanced(top, g, ng, static_cast<const double*>(w), gid, n, static_cast<const bvh_ray3d*>(rays), nr, f, static_cast<bvh_hit3d*>(hits), inst, nullptr, nullptr); }
-    static int visit(const Handle* h, const void* ray, size_t start, unsigned f, void* user, bool (*leaf)(void*, double*, size_t, size_t), void (*inner)(void*, size_t)) {
-        const bvh_amd_ray_visitord v{ user, leaf, inner };
-        return bvh3d_intersect_ray_visit(h, static_cast<const bvh_ray3d*>(ray), start, f, &v);
-    }
-};
-
+BVH_AMD_API_3D(float, 3f)
+BVH_AMD_API_3D(double, 3d)
+#undef BVH_AMD_API_3D
 
 #define BVH_AMD_API_2D(T, S)                                                                                                              \
 template <> struct Api<T, 2> {                                                                                                            \

@@ -1,5 +1,7 @@
-// TEST INFRASTRUCTURE (CPU, no GPU): what the host harnesses of the point, box and instanced queries (closest_body_host.cpp,
-// radius_body_host.cpp, knn_body_host.cpp, overlap_body_host.cpp, instanced_body_host.cpp) put in front of the kernels' text:
+// TEST INFRASTRUCTURE (CPU, no GPU): what the host harnesses of the one-lane-per-query kinds (closest_body_host.cpp,
+// radius_body_host.cpp, knn_body_host.cpp, overlap_body_host.cpp, tri_intersect_body_host.cpp, tri_distance_body_host.cpp,
+// region_body_host.cpp, winding_body_host.cpp, ray_hits_body_host.cpp, ray_nearest_body_host.cpp, sphere_cast_body_host.cpp,
+// instanced_body_host.cpp; every *_body_host.cpp but trace_body_host.cpp and refit_body_host.cpp) put in front of the kernels' text:
 // single-lane stand-ins for hip_runtime.h and for bvh_amd/csrc/common.h, then the device helpers of bvh_amd/csrc/trace_device.h, the
 // thread-split scaffold of their walks, and the emulation of one launch of a sliced batch over a deep tree. The stand-ins must follow
 // common.h (PairNode, kCountBits, LEAF_*).
