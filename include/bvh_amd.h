@@ -919,6 +919,10 @@ BVH_AMD_API int bvh3d_intersect_rays_nearest_sphere(const struct bvh3d*, const d
  *   flags:   BVH_AMD_RAY_ROBUST (the robust box test), BVH_AMD_RAY_ORIGINAL_IDS, BVH_AMD_RAY_SORTED / BVH_AMD_RAY_UNSORTED (the
  *            reordering key of the all-hits query; with neither, batches of >= 1M queries are reordered). Any other bit:
  *            BVH_AMD_ERR_ARG. n == 0 is a no-op.
+ *   t < 0:   with BVH_AMD_RAY_ROBUST no contact at t >= 0 is lost to the box test; below 0 (a negative tmin) a box thinner than the
+ *            padding of the inverse direction, such as the box of an axis-aligned triangle under r = 0, can be skipped, because the
+ *            padding moves a slab's exit outward only where t >= 0. What IS reported there is still a contact. Start the ray
+ *            further back (tmin >= 0) where contacts behind the origin matter.
  * A query's record depends only on the tree, the primitives, the ray, its radius and ROBUST / ORIGINAL_IDS: not on batch size,
  * position or order, the reordering flags, the stream or the thread. d_counters (optional) receives {pair records fetched, primitives
  * tested, leaves visited}. Alignment: d_prims and d_rays 16 bytes, d_hits to the size of its record (16 / 32), d_counters 8, d_radii

@@ -55,6 +55,12 @@ def slices(n, per):
     return [(first, min(per, n - first)) for first in range(0, n, per)]
 
 
+def mesh_entry(query, scalar_bytes):
+    """Bytes per spilled stack entry of the mesh queries, as their drivers hand it to point_query_run: sphere_cast.hip and
+    tri_distance.hip keep the key beside the node (sizeof(uint32_t) + sizeof(T): nearest_walk.inc), region.hip the node alone."""
+    return {"sphere_cast": 4 + scalar_bytes, "tri_distance": 4 + scalar_bytes, "region": 4}[query]
+
+
 # ---- scenes -----------------------------------------------------------------------------------------------------------------------
 
 def chain_base(depth):
@@ -170,6 +176,36 @@ def mixed_boxes(depth, n, dtype):
     near = ~np.isin(i % 8, (3, 6))
     q[near, 0], q[near, 3] = chain_base(depth) - 0.25, chain_base(depth) + 1
     return q
+
+
+def cast_rays(depth, n, dtype):
+    """For sphere_cast over `chain`: balls flying along +x from x in [0, 100) towards the far end of the chain (they enter the rest of
+    the chain before each level's leaf and stack one entry per level; the deepest triangle is the first one met), radius 0.25 or 0;
+    every 7th passes 5 units beside the chain (it fails the root's boxes), every 11th ends at tmax = 10, far short of it.
+    -> (rays (n, 8), radii (n,))."""
+    rng = np.random.default_rng(depth + 3)
+    r = np.zeros((n, 8), dtype=dtype)
+    r[:, 0] = rng.integers(0, 100, n)
+    r[:, 1:3] = rng.integers(-2, 3, (n, 2)) / 4.0
+    r[:, 3], r[:, 7] = 1.0, np.inf
+    r[::7, 1] = 5.0
+    r[::11, 7] = 10.0
+    radii = np.where(np.arange(n) % 3 == 0, 0.0, 0.25).astype(dtype)
+    return r, radii
+
+
+def region_planes(depth, n, dtype):
+    """For the region queries over tri_intersect_ref.chain_tree (stacked): z <= -0.5 cuts every triangle of the chain; a second plane
+    x <= the far end + a little keeps a few levels, and every 64th region has none: every level (a list of depth + 1 entries, one
+    stacked leaf per level). Every other 5th region is x <= 1: nothing. -> (n, 2, 4)."""
+    rng = np.random.default_rng(depth + 4)
+    planes = np.zeros((n, 2, 4), dtype=dtype)
+    planes[:, 0] = [0, 0, 1, 0.5]
+    planes[:, 1, 0] = 1
+    planes[:, 1, 3] = -(chain_base(depth) - depth + 10 * rng.random(n))
+    planes[::5, 1, 3] = -1.0
+    planes[3::64, 1] = [0, 0, 0, 0]
+    return planes
 
 
 def box_chain(depth, dtype, ids):

@@ -562,3 +562,130 @@ def test_refit_then_sorted_query_on_a_side_stream(dlls):
     stream.synchronize()
     assert bvh_amd.hits_to_numpy(hits).tobytes() == want.tobytes()
     assert (want["prim"] != INVALID).all()
+
+
+# ---- the mesh queries: sphere_cast, tri_distance, region ------------------------------------------------------------------------------
+# Their spill is indexed by the lane of the launch like that of the point queries. Expected: byte equality with the device's own
+# results for the same queries submitted one launch per call, counters summed; byte equality with the host harness on every 15th
+# query (the harness walks one query at a time: a sixteenth of 3 * per_launch queries over 3000 levels is about what a test can
+# afford, and 15 shares no factor with the periods of the batches below, so every kind of query is among those compared).
+SAMPLE = 15
+
+MESH_FLAGS = {"sphere_cast": (0, SORTED | ROBUST, ORIGINAL_IDS), "tri_distance": (0, SORTED, ORIGINAL_IDS), "region": (0, 64, ORIGINAL_IDS)}
+
+
+def mesh_device(bvh, dtype):
+    """test_gpu_mesh_query_fuzz.Device (the C entry points, every output between guard zones) that notes the launches of its calls."""
+    from test_gpu_mesh_query_fuzz import Device as MeshDevice
+    dev = MeshDevice(bvh, dtype)
+    dev.lib = Counting(dev.lib)
+    return dev
+
+
+@pytest.fixture(scope="module")
+def mesh_dlls(tmp_path_factory):
+    import region_ref
+    import test_sphere_cast_host as cast_host
+    import test_tri_distance_host as dist_host
+    d = tmp_path_factory.mktemp("mesh_query_slices_gpu")
+    return {"cast": cast_host.compile_harness(d), "distance": dist_host.compile_harness(d), "region": region_ref.compile_harness(d)}
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
+def test_sphere_cast(mesh_dlls, chains, dtype):
+    import test_sphere_cast_host as cast_host
+    bvh, nodes, prims, ids, dprims = chains(dtype, False)
+    per, n = sizes(qs.mesh_entry("sphere_cast", np.dtype(dtype).itemsize))
+    cap = qs.deep_cap(DEPTH)
+    rays, radii = qs.cast_rays(DEPTH, n, dtype)
+    for flags in MESH_FLAGS["sphere_cast"]:
+        dev = mesh_device(bvh, dtype)
+        hits, cnt = dev.cast(dprims, 0, rays, radii, flags)
+        assert dev.lib.launches == [4], (flags, dev.lib.launches)
+        parts = []
+        for first, m in qs.slices(n, per):                     # the same rays, one launch per call
+            part = mesh_device(bvh, dtype)
+            parts.append(part.cast(dprims, 0, rays[first:first + m], radii[first:first + m], flags))
+            assert part.lib.launches == [1], (flags, first, part.lib.launches)
+        assert np.concatenate([p[0] for p in parts]).tobytes() == hits.tobytes(), flags
+        assert (np.sum([p[1] for p in parts], axis=0) == cnt).all(), flags
+        want, _ = cast_host.host_walk(mesh_dlls["cast"], nodes["bounds"], nodes["index"], prims, rays[::SAMPLE], radii[::SAMPLE], 0, robust=bool(flags & ROBUST),
+                                      prim_ids=ids if flags & ORIGINAL_IDS else None, deep_cap=cap, threads=HOST_THREADS)
+        assert hits[::SAMPLE].tobytes() == want.tobytes(), flags
+        if flags == 0:
+            i = np.arange(n)
+            through = (i % 7 != 0) & (i % 11 != 0)
+            ball = through & (radii > 0)                       # (a bare ray at |y| = 0.5, z = 0.5 passes beside every triangle)
+            assert (hits["prim"][ball] == DEPTH).all() and (hits["prim"][~through] == INVALID).all()         # the deepest triangle is the first one met
+            assert np.isin(hits["prim"], (DEPTH, INVALID)).all() and ball[-37:].sum() >= 8
+    report(f"sphere_cast {np.dtype(dtype).name}", n, per, dev.lib.launches[-1])
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
+def test_tri_distance(mesh_dlls, dtype):
+    import test_tri_distance_host as dist_host
+    import tri_intersect_ref as TR
+    from test_gpu_tri_distance import device_tree
+    tree = TR.chain_tree(DEPTH, dtype, stacked=True, ids=qs.prim_ids(DEPTH + 1))
+    bvh = device_tree(tree)
+    dtris = _cuda(tree.tris)
+    per, n = sizes(qs.mesh_entry("tri_distance", np.dtype(dtype).itemsize))
+    cap = qs.deep_cap(DEPTH)
+    q = dist_host.chain_queries(DEPTH, n).astype(dtype)
+    lim = np.where(np.arange(n) % 3 == 0, 2.0, np.inf).astype(dtype)
+    for flags in MESH_FLAGS["tri_distance"]:
+        dev = mesh_device(bvh, dtype)
+        hits, uv, cnt = dev.distance(dtris, q, lim, flags)
+        assert dev.lib.launches == [4], (flags, dev.lib.launches)
+        parts = []
+        for first, m in qs.slices(n, per):
+            part = mesh_device(bvh, dtype)
+            parts.append(part.distance(dtris, q[first:first + m], lim[first:first + m], flags))
+            assert part.lib.launches == [1], (flags, first, part.lib.launches)
+        assert np.concatenate([p[0] for p in parts]).tobytes() == hits.tobytes() and np.concatenate([p[1] for p in parts]).tobytes() == uv.tobytes(), flags
+        assert (np.sum([p[2] for p in parts], axis=0) == cnt).all(), flags
+        want, want_uv, _ = dist_host.host_walk(mesh_dlls["distance"], tree, q[::SAMPLE], lim[::SAMPLE], original_ids=bool(flags & ORIGINAL_IDS), deep_cap=cap,
+                                               threads=HOST_THREADS)
+        assert hits[::SAMPLE].tobytes() == want.tobytes() and uv[::SAMPLE].tobytes() == want_uv.tobytes(), flags
+        if flags == 0:
+            assert (hits["t"][::4] == 0).all() and (hits["prim"][::4] == 0).all()        # the sliver crosses every level: the lowest index wins
+            assert (hits["t"][-37:] > 0).sum() >= 8
+    report(f"tri_distance {np.dtype(dtype).name}", n, per, dev.lib.launches[-1])
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
+def test_region(mesh_dlls, dtype):
+    """The count pass and the fill pass (lists and inside bytes between guard zones: test_gpu_mesh_query_fuzz.Device.region)."""
+    import region_ref
+    import tri_intersect_ref as TR
+    from test_gpu_region import device_tree
+    t = TR.chain_tree(DEPTH, dtype, stacked=True, ids=qs.prim_ids(DEPTH + 1))
+    tree = region_ref.PrimTree(t.bounds, t.index, t.tris, t.ids)
+    bvh = device_tree(tree)
+    dprims = _cuda(tree.prims)
+    per, n = sizes(qs.mesh_entry("region", np.dtype(dtype).itemsize))
+    cap = qs.deep_cap(DEPTH)
+    planes = qs.region_planes(DEPTH, n, dtype)
+    for flags in MESH_FLAGS["region"]:
+        dev = mesh_device(bvh, dtype)
+        offsets, lst, ins, counts, cnt = dev.region(dprims, 0, planes, flags)
+        assert dev.lib.launches == [4, 4], (flags, dev.lib.launches)                     # the count pass and the fill pass
+        parts = []
+        for first, m in qs.slices(n, per):
+            part = mesh_device(bvh, dtype)
+            parts.append(part.region(dprims, 0, planes[first:first + m], flags))
+            assert part.lib.launches == [1, 1], (flags, first, part.lib.launches)
+        for j, whole in ((1, lst), (2, ins), (3, counts)):
+            assert np.concatenate([p[j] for p in parts]).tobytes() == whole.tobytes(), (flags, j)
+        assert (np.sum([p[4] for p in parts], axis=0) == cnt).all(), flags
+        h_off, h_lst, h_ins, h_counts, _ = region_ref.host_region(mesh_dlls["region"], tree, planes[::SAMPLE], exact=bool(flags & 64),
+                                                                  original_ids=bool(flags & ORIGINAL_IDS), deep_cap=cap, threads=HOST_THREADS)
+        assert (counts[::SAMPLE] == h_counts).all(), flags
+        pick = np.concatenate([np.arange(int(offsets[k]), int(offsets[k + 1])) for k in range(0, n, SAMPLE)]).astype(np.int64)
+        assert lst[pick].tobytes() == h_lst.tobytes() and ins[pick].tobytes() == h_ins.tobytes(), flags
+        if flags == 0:
+            i = np.arange(n)
+            everything, nothing = i % 64 == 3, (i % 5 == 0) & (i % 64 != 3)
+            assert (counts[everything] == DEPTH + 1).all() and (counts[nothing] == 0).all() and np.flatnonzero(everything)[-1] >= n - 37
+            assert 0 < counts[~everything & ~nothing].min() and counts[~everything].max() < 16
+    report(f"region {np.dtype(dtype).name}", n, per, dev.lib.launches[-1])
